@@ -8,11 +8,17 @@ BASELINE.json -- one synthetic 512x512 frame per GPU, 778-vertex hand + 10 242-v
 (image-sharded: rank r owns its own frame, no data-path collective; one RCCL all-reduce of the metrics
 vector at the end of the batch).
 
-    python bench.py --gpus 1 --steps 50 --warmup 5
+    python bench.py --gpus 1 --steps 50 --warmup 5 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (stdout): the contract's fields + `roofline` + `cpu_baseline` + `parity`, kept under 1 900 characters
-so that it survives whole in a log tail (`roofline.secondary` carries the headline numbers of the side records).  The DETAIL
+A plain run sets up, warms up, times EXACTLY --steps iterations once (`ms_per_step` = that region / steps; the last one
+starts from a restart, so that what it computes is the same in every run), writes the outputs of the last timed step if
+--dump-outputs is given and prints the line: nothing else runs.  --full adds what the
+headline figure does not need: the timed region repeated until it has measured MIN_TIMED_S (the median repeat is
+reported), the per-kernel roofline, the side records and the CPU baseline + parity below.
+
+Prints ONE JSON line on rank 0 (stdout): the contract's fields (+ `roofline` + `cpu_baseline` + `parity` with --full), kept under
+1 900 characters so that it survives whole in a log tail (`roofline.secondary` carries the headline numbers of the side records).  The DETAIL
 record -- everything below -- goes to stderr as one line prefixed `bench-detail: ` and to gpurun_out/bench_detail.json:
   roofline            the dominant kernel: algorithmic bytes per launch / hipEvent-timed duration on the launch stream
   kernels             every launch of the step the same way
@@ -227,10 +233,18 @@ def pick_spg(steps, cap=0):
     return min(spg, cap) if cap > 0 else spg
 
 
-def make_runner(E, torch, scenes, n_streams, dev, cfg, spg, graph=True, joint=False, **kw):
+def make_runner(E, torch, scenes, n_streams, dev, cfg, spg, graph=True, joint=False, tail=0, **kw):
+    """tail > 1: one more hipGraph per stream of `tail` iterations, replayed for a chunk whose last `tail` iterations do not
+    fill a graph of `spg` (instead of `tail` single-iteration replays)."""
     group = E.GuidanceGroup(scenes, n_streams, device=dev, **kw)
+    tails = []
     if graph:
         group.capture(cfg, joint=joint, steps_per_graph=spg)
+        if not joint and spg > 1 and tail > 1:
+            for gb, st in zip(group.batches, group.streams):
+                with torch.cuda.stream(st):
+                    tails.append(gb.capture(cfg, steps_per_graph=tail))
+            torch.cuda.synchronize(dev)
     ident = torch.tensor([1, 0, 0, 0, 1, 0, 0, 0] * 2, dtype=torch.float32, device=dev)  # PL:1207-1215
 
     state = {"it": 0}
@@ -248,7 +262,13 @@ def make_runner(E, torch, scenes, n_streams, dev, cfg, spg, graph=True, joint=Fa
             if state["it"] % window == 0:
                 group.restart(ident)
             k = min(window - state["it"] % window, n - done)
-            group.run(cfg, k)
+            if tails and k % spg == tail:
+                group.run(cfg, k - tail)
+                for g, st in zip(tails, group.streams):
+                    with torch.cuda.stream(st):
+                        g.replay()
+            else:
+                group.run(cfg, k)
             done += k
             state["it"] += k
 
@@ -274,10 +294,16 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the batched / topology_changing sub-records")
     ap.add_argument("--cpu-steps", type=int, default=30)
-    ap.add_argument("--repeats", type=int, default=0, help="repeats of the timed region (0 = as many as it takes to measure "
-                    f"{MIN_TIMED_S} s; the median repeat is reported)")
+    ap.add_argument("--repeats", type=int, default=None, help="repeats of the timed region (0 = as many as it takes to measure "
+                    f"{MIN_TIMED_S} s; the median repeat is reported).  Default: 1, with --full 0")
     ap.add_argument("--gbuf-f16", action="store_true", help="depth / colour planes of the G-buffer in fp16 (configs[4])")
+    ap.add_argument("--full", action="store_true", help="measure beyond the headline figure: repeated timed regions, per-kernel "
+                    "roofline, side records (unless --no-extras), CPU baseline and parity (unless --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step left for its caller (rank 0's images) "
+                    "as DIR/<name>.npy, float32 / float64")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 0 if args.full else 1
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))          # plain `python bench.py --gpus N`: this process becomes the launcher
@@ -336,16 +362,28 @@ def main():
     # iterations per hipGraph: the reference's inner loop is 50 iterations per denoising step, and nothing in the step
     # needs the host, so a slice of that loop is ONE graph replay (no host work between iterations)
     spg = 1 if (args.no_graph or args.joint_graph) else pick_spg(args.steps, args.steps_per_graph)
+    # the timed path ends with a restart and ONE iteration (run_timed): the K - 1 before it leave (K - 1) % spg iterations
+    # after their last full graph, replayed as one graph of their own
     group, run_steps = make_runner(E, torch, scenes, n_streams, dev, cfg, spg, graph=not args.no_graph, joint=args.joint_graph,
-                                   gbuf_f16=args.gbuf_f16)
+                                   tail=(args.steps - 1) % spg if spg > 1 else 0, gbuf_f16=args.gbuf_f16)
     gb = group.batches[0]
 
     run_steps(50)            # setup: let clocks / caches settle before the counted warm-up
     torch.cuda.synchronize(dev)
 
     run_steps(args.warmup)
-    run_steps.realign()      # timed regions start on a window boundary: every chunk stays a multiple of the graph length
     torch.cuda.synchronize(dev)
+
+    def run_timed(n):
+        """The timed path: n iterations in the 50-iteration windows of the workload, each window starting with a restart
+        (scene start point, fresh AdamW), the LAST iteration in a window of its own.  Its inputs are then the same in every
+        run: the float atomics of k_pix_bwd leave ~1e-7 of run-to-run noise per iteration, which the
+        optimisation at the reference's learning rates amplifies to O(1) within ~10 iterations of a restart, so what the
+        last iteration of a longer window computes would differ from run to run."""
+        run_steps.realign()
+        run_steps(n - 1)
+        run_steps.realign()
+        run_steps(1)
 
     def timed_region():
         """EXACTLY args.steps iterations between barrier + synchronize on both sides; max over ranks."""
@@ -353,7 +391,7 @@ def main():
             dist.barrier()
         torch.cuda.synchronize(dev)
         t0 = time.perf_counter()
-        run_steps(args.steps)
+        run_timed(args.steps)
         torch.cuda.synchronize(dev)
         if dist is not None:
             dist.barrier()
@@ -363,9 +401,10 @@ def main():
             dist.all_reduce(tm, op=dist.ReduceOp.MAX)
         return float(tm.item())
 
-    # A short --steps (the driver's 20) is a ~1 ms region -- two graph replays, at the mercy of one scheduling hiccup.  The
-    # region is therefore repeated until MIN_TIMED_S has been measured and the MEDIAN repeat is reported; every repeat is
-    # the contract's region (K steps, barriers, max over ranks), `steps` stays K.  The repeat count follows from the first
+    # A plain run times the region once: --steps is the number of timed iterations.  With --full (or --repeats 0), a short
+    # --steps (the driver's 20) is a ~1 ms region -- two graph replays, at the mercy of one scheduling hiccup -- so the
+    # region is repeated until MIN_TIMED_S has been measured and the MEDIAN repeat is reported; every repeat is the
+    # contract's region (K steps, barriers, max over ranks), `steps` stays K.  The repeat count follows from the first
     # repeat's all-reduced time, so every rank arrives at the same number.
     times = [timed_region()]
     n_rep = int(min(200, max(1, -(-MIN_TIMED_S // max(times[0], 1e-6))))) if args.repeats <= 0 else args.repeats
@@ -381,6 +420,8 @@ def main():
         metrics = sharding.all_reduce_metrics(metrics, dist)
     for g in group.batches:
         g.raise_on_flags()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, group, np)      # before anything below runs another step
 
     m0 = gb.meta[0]
     value = world * ipg * args.steps / dt
@@ -401,113 +442,139 @@ def main():
     }
 
     if rank == 0:
-        sizes = (H, W, m0["Vh"], m0["Vo"], m0["Fh"], m0["Fo"])
-        # ---- roofline of the dominant kernel: hipEvents around every launch, averaged over the timed step count
-        acc, samples = {}, {}
-        nprof = 100
-        run_steps(25)            # profile in the middle of a 50-iteration window
-        torch.cuda.synchronize(dev)
-        cfg_frozen, _ = E.phase_cfg("C", denoise_i=19, do_update=False)
-        for _ in range(nprof):      # timed the way the iterations run inside the multi-iteration graphs (deferred final stage)
-            for k, v in gb.step_profiled(cfg_frozen, deferred=spg > 1).items():
-                acc[k] = acc.get(k, 0.0) + v / nprof
-                samples.setdefault(k, []).append(v)
-        # hit statistics of the profiled scene (the G-buffer is hit-only): hit pixels and pixels of 32x8 tiles with a hit
-        P = H * W
-        p2f = gb.region("p2f", torch.int32, (2, gb.B, H, W))[:, 0]
-        hits = {"px": [int((p2f[r] >= 0).sum()) for r in range(2)], "tile_px": []}
-        for r in range(2):
-            t = (p2f[r] >= 0)[: H // 8 * 8, : W // 32 * 32].reshape(H // 8, 8, W // 32, 32).any(3).any(1)
-            hits["tile_px"].append(int(t.sum()) * 256)
-        # the dominant kernel is picked LIVE, by the MEDIAN of the profiled launches (one disturbed launch in the sample must
-        # not change which kernel the record is about); the roofline figures use the mean, as the contract asks.  What the
-        # committed rocprofv3 kernel trace of the same workload says is reported beside it (`dominant_by_trace`): event
-        # timing adds ~3 us per launch and reads k_pix_bwd high in about one process out of six, so the two can differ -- the
-        # record says so instead of hiding it.
-        med = {k: float(np.median(v)) for k, v in samples.items()}
-        dom = max(med, key=lambda k: med[k])
-        workload = (args.obj, args.size, gb.B)       # object, image size, images per LAUNCH (the profiled batch)
-        prof_dom, prof_src = dominant_from_kernel_stats(set(acc), workload)
-        kb = kernel_bytes(dom, *sizes, hits=hits)
-        bstep = algorithmic_bytes(*sizes)
-        if kb is None:
-            kb = bstep
-        ipb = gb.B               # images in the profiled batch (the first stream's)
-        achieved = kb * ipb / (acc[dom] * 1e-3) / 1e9
-        pmc, pmc_src = pmc_table(workload)
-        ea, ea_src = ea_table(workload)
-        out["roofline"] = {"bound": "hbm", "roof": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                           "frac": achieved / HBM_PEAK_GBS, "traffic": pmc.get(dom),
-                           "traffic_source": f"{pmc_src} (2*FETCH_SIZE+WRITE_SIZE, KiB)" if pmc_src else None,
-                           "traffic_by_request_size": ea.get(dom), "traffic_by_request_size_source": ea_src,
-                           "kernel_ms": acc[dom], "kernel_ms_median": med[dom], "algorithmic_bytes_per_launch": kb * ipb,
-                           "dominant_by_trace": prof_dom, "trace_source": prof_src}
-        sq, sq_src = sq_table(workload)
-        vr = valu_roofline(sq, acc, ipb)
-        if vr:
-            tot_busy = sum(v["valu_busy_simd_cycles"] for v in vr.values())
-            out["roofline_valu"] = {"bound": "valu-issue", "kernel": dom, "frac": vr.get(dom, {}).get("valu_frac"), "kernels": vr,
-                                    "step_valu_wave_instructions": sum(v["valu_wave_instructions"] for v in vr.values()),
-                                    "step_valu_frac": tot_busy / ipb * value / world / VALU_PEAK_CYCLES_PER_S, "source": sq_src,
-                                    "peak": "1024 SIMDs x 2.4 GHz busy cycles/s (SQ_ACTIVE_INST_VALU x 4 per launch / live duration)"}
-            hb, vf = out["roofline"]["frac"], vr.get(dom, {}).get("valu_frac") or 0.0
-            # what binds: neither roof is near at one image per launch -- the kernels wait (wait_frac) on chains of dependent
-            # round trips; the record says so instead of letting "bound": "hbm" stand alone
-            # `bound` names what binds: at one image per launch neither roof does (the HBM figures are quoted against `roof`)
-            if hb < 0.25 and vf < 0.5:
-                out["roofline"]["bound"] = "latency"
-            elif vf >= 0.5:
-                out["roofline"]["bound"] = "valu-issue"
-            out["roofline"]["binding"] = (f"latency: {dom} uses {hb:.3f} of the HBM roof and {vf:.3f} of the VALU-issue roof, "
-                                          f"its waves wait {vr.get(dom, {}).get('wait_frac') or 0:.2f} of their life (SQ_WAIT_ANY)")
-        out["kernel_ms"] = {k: round(v, 5) for k, v in acc.items()}
-        out["kernel_ms_median"] = {k: round(v, 5) for k, v in med.items()}
-        out["hit_pixels"] = hits
-        out["kernels"] = {}
-        for k, v in acc.items():           # every launch of the step against the HBM roofline (algorithmic bytes / duration)
-            kbk = kernel_bytes(k, *sizes, hits=hits) or 0
-            gbs = kbk * ipb / (v * 1e-3) / 1e9
-            out["kernels"][k] = {"ms": round(v, 5), "algorithmic_MB": round(kbk * ipb / 1e6, 3), "GBs": round(gbs, 1),
-                                 "frac": round(gbs / HBM_PEAK_GBS, 4),
-                                 "traffic_MB": round(pmc[k] / 1e6, 3) if k in pmc else None,
-                                 "traffic_by_request_size_MB": round(ea[k] / 1e6, 3) if k in ea else None}
-        out["step_hbm_GBs"] = bstep * value / world / 1e9  # whole-step algorithmic bytes x steps/s per GPU
-        out["step_roofline_frac"] = out["step_hbm_GBs"] / HBM_PEAK_GBS
-        if pmc:
-            step_traffic = sum(pmc.get(k, 0.0) for k in acc)
-            out["step_traffic_MB"] = round(step_traffic / 1e6, 3)
-            out["step_traffic_frac"] = step_traffic * value / world / 1e9 / HBM_PEAK_GBS
+        if args.full:
+            sizes = (H, W, m0["Vh"], m0["Vo"], m0["Fh"], m0["Fo"])
+            # ---- roofline of the dominant kernel: hipEvents around every launch, averaged over the timed step count
+            acc, samples = {}, {}
+            nprof = 100
+            run_steps(25)            # profile in the middle of a 50-iteration window
+            torch.cuda.synchronize(dev)
+            cfg_frozen, _ = E.phase_cfg("C", denoise_i=19, do_update=False)
+            for _ in range(nprof):      # timed the way the iterations run inside the multi-iteration graphs (deferred final stage)
+                for k, v in gb.step_profiled(cfg_frozen, deferred=spg > 1).items():
+                    acc[k] = acc.get(k, 0.0) + v / nprof
+                    samples.setdefault(k, []).append(v)
+            # hit statistics of the profiled scene (the G-buffer is hit-only): hit pixels and pixels of 32x8 tiles with a hit
+            P = H * W
+            p2f = gb.region("p2f", torch.int32, (2, gb.B, H, W))[:, 0]
+            hits = {"px": [int((p2f[r] >= 0).sum()) for r in range(2)], "tile_px": []}
+            for r in range(2):
+                t = (p2f[r] >= 0)[: H // 8 * 8, : W // 32 * 32].reshape(H // 8, 8, W // 32, 32).any(3).any(1)
+                hits["tile_px"].append(int(t.sum()) * 256)
+            # the dominant kernel is picked LIVE, by the MEDIAN of the profiled launches (one disturbed launch in the sample must
+            # not change which kernel the record is about); the roofline figures use the mean, as the contract asks.  What the
+            # committed rocprofv3 kernel trace of the same workload says is reported beside it (`dominant_by_trace`): event
+            # timing adds ~3 us per launch and reads k_pix_bwd high in about one process out of six, so the two can differ -- the
+            # record says so instead of hiding it.
+            med = {k: float(np.median(v)) for k, v in samples.items()}
+            dom = max(med, key=lambda k: med[k])
+            workload = (args.obj, args.size, gb.B)       # object, image size, images per LAUNCH (the profiled batch)
+            prof_dom, prof_src = dominant_from_kernel_stats(set(acc), workload)
+            kb = kernel_bytes(dom, *sizes, hits=hits)
+            bstep = algorithmic_bytes(*sizes)
+            if kb is None:
+                kb = bstep
+            ipb = gb.B               # images in the profiled batch (the first stream's)
+            achieved = kb * ipb / (acc[dom] * 1e-3) / 1e9
+            pmc, pmc_src = pmc_table(workload)
+            ea, ea_src = ea_table(workload)
+            out["roofline"] = {"bound": "hbm", "roof": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": achieved / HBM_PEAK_GBS, "traffic": pmc.get(dom),
+                               "traffic_source": f"{pmc_src} (2*FETCH_SIZE+WRITE_SIZE, KiB)" if pmc_src else None,
+                               "traffic_by_request_size": ea.get(dom), "traffic_by_request_size_source": ea_src,
+                               "kernel_ms": acc[dom], "kernel_ms_median": med[dom], "algorithmic_bytes_per_launch": kb * ipb,
+                               "dominant_by_trace": prof_dom, "trace_source": prof_src}
+            sq, sq_src = sq_table(workload)
+            vr = valu_roofline(sq, acc, ipb)
+            if vr:
+                tot_busy = sum(v["valu_busy_simd_cycles"] for v in vr.values())
+                out["roofline_valu"] = {"bound": "valu-issue", "kernel": dom, "frac": vr.get(dom, {}).get("valu_frac"), "kernels": vr,
+                                        "step_valu_wave_instructions": sum(v["valu_wave_instructions"] for v in vr.values()),
+                                        "step_valu_frac": tot_busy / ipb * value / world / VALU_PEAK_CYCLES_PER_S, "source": sq_src,
+                                        "peak": "1024 SIMDs x 2.4 GHz busy cycles/s (SQ_ACTIVE_INST_VALU x 4 per launch / live duration)"}
+                hb, vf = out["roofline"]["frac"], vr.get(dom, {}).get("valu_frac") or 0.0
+                # what binds: neither roof is near at one image per launch -- the kernels wait (wait_frac) on chains of dependent
+                # round trips; the record says so instead of letting "bound": "hbm" stand alone
+                # `bound` names what binds: at one image per launch neither roof does (the HBM figures are quoted against `roof`)
+                if hb < 0.25 and vf < 0.5:
+                    out["roofline"]["bound"] = "latency"
+                elif vf >= 0.5:
+                    out["roofline"]["bound"] = "valu-issue"
+                out["roofline"]["binding"] = (f"latency: {dom} uses {hb:.3f} of the HBM roof and {vf:.3f} of the VALU-issue roof, "
+                                              f"its waves wait {vr.get(dom, {}).get('wait_frac') or 0:.2f} of their life (SQ_WAIT_ANY)")
+            out["kernel_ms"] = {k: round(v, 5) for k, v in acc.items()}
+            out["kernel_ms_median"] = {k: round(v, 5) for k, v in med.items()}
+            out["hit_pixels"] = hits
+            out["kernels"] = {}
+            for k, v in acc.items():           # every launch of the step against the HBM roofline (algorithmic bytes / duration)
+                kbk = kernel_bytes(k, *sizes, hits=hits) or 0
+                gbs = kbk * ipb / (v * 1e-3) / 1e9
+                out["kernels"][k] = {"ms": round(v, 5), "algorithmic_MB": round(kbk * ipb / 1e6, 3), "GBs": round(gbs, 1),
+                                     "frac": round(gbs / HBM_PEAK_GBS, 4),
+                                     "traffic_MB": round(pmc[k] / 1e6, 3) if k in pmc else None,
+                                     "traffic_by_request_size_MB": round(ea[k] / 1e6, 3) if k in ea else None}
+            out["step_hbm_GBs"] = bstep * value / world / 1e9  # whole-step algorithmic bytes x steps/s per GPU
+            out["step_roofline_frac"] = out["step_hbm_GBs"] / HBM_PEAK_GBS
+            if pmc:
+                step_traffic = sum(pmc.get(k, 0.0) for k in acc)
+                out["step_traffic_MB"] = round(step_traffic / 1e6, 3)
+                out["step_traffic_frac"] = step_traffic * value / world / 1e9 / HBM_PEAK_GBS
 
-        if world == 1 and not args.no_extras:
-            # side records: a failure in one of them (a raised step flag, say) is reported in its place and must not cost
-            # the headline line above
-            for key, fn in (("batched", lambda: batched_record(E, torch, synthetic, render_fn, args, dev, cfg)),
-                            ("batched_f16_gbuffer", lambda: batched_record(E, torch, synthetic, render_fn, args, dev, cfg, gbuf_f16=True)),
-                            ("topology_changing", lambda: topology_record(E, torch, scenes[0], dev)),
-                            ("closeup", lambda: closeup_record(E, torch, np, synthetic, render_fn, args, dev, cfg)),
-                            ("obj_40k", lambda: obj40k_record(E, torch, synthetic, render_fn, args, dev, cfg)),
-                            ("geo_decode", lambda: geo_decode_record(torch, dev)),
-                            ("vae_attention", lambda: vae_attention_record(torch, dev)),
-                            ("vae_transformer", lambda: vae_transformer_record(torch, dev)),
-                            ("icp", lambda: icp_record(torch, np, dev)),
-                            ("lbs", lambda: lbs_record(torch, np, synthetic, dev)),
-                            ("pipeline_iteration", lambda: pipeline_iteration_record(E, torch, scenes[0], dev)),
-                            ("final_decode", lambda: final_decode_record(torch, np, dev)),
-                            ("job", lambda: job_record(E, torch, synthetic, render_fn, args, dev)),
-                            ("driver_on_files", lambda: driver_record(E, torch, np, synthetic, render_fn, args))):
-                try:
-                    out[key] = fn()
-                except Exception as e:  # noqa: BLE001
-                    out[key] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and not args.no_cpu_baseline:
-            base, first = cpu_baseline(scenes[0], args.cpu_steps)
-            out["cpu_baseline"] = base
-            out["parity"] = parity_record(E, torch, np, scenes[0], dev, first)
-            out["cpu_baseline_1t"] = cpu_baseline(scenes[0], 5, threads=1, budget_s=20.0)[0]
+            if world == 1 and not args.no_extras:
+                # side records: a failure in one of them (a raised step flag, say) is reported in its place and must not cost
+                # the headline line above
+                for key, fn in (("batched", lambda: batched_record(E, torch, synthetic, render_fn, args, dev, cfg)),
+                                ("batched_f16_gbuffer", lambda: batched_record(E, torch, synthetic, render_fn, args, dev, cfg, gbuf_f16=True)),
+                                ("topology_changing", lambda: topology_record(E, torch, scenes[0], dev)),
+                                ("closeup", lambda: closeup_record(E, torch, np, synthetic, render_fn, args, dev, cfg)),
+                                ("obj_40k", lambda: obj40k_record(E, torch, synthetic, render_fn, args, dev, cfg)),
+                                ("geo_decode", lambda: geo_decode_record(torch, dev)),
+                                ("vae_attention", lambda: vae_attention_record(torch, dev)),
+                                ("vae_transformer", lambda: vae_transformer_record(torch, dev)),
+                                ("icp", lambda: icp_record(torch, np, dev)),
+                                ("lbs", lambda: lbs_record(torch, np, synthetic, dev)),
+                                ("pipeline_iteration", lambda: pipeline_iteration_record(E, torch, scenes[0], dev)),
+                                ("final_decode", lambda: final_decode_record(torch, np, dev)),
+                                ("job", lambda: job_record(E, torch, synthetic, render_fn, args, dev)),
+                                ("driver_on_files", lambda: driver_record(E, torch, np, synthetic, render_fn, args))):
+                    try:
+                        out[key] = fn()
+                    except Exception as e:  # noqa: BLE001
+                        out[key] = {"error": f"{type(e).__name__}: {e}"}
+            if world == 1 and not args.no_cpu_baseline:
+                base, first = cpu_baseline(scenes[0], args.cpu_steps)
+                out["cpu_baseline"] = base
+                out["parity"] = parity_record(E, torch, np, scenes[0], dev, first)
+                out["cpu_baseline_1t"] = cpu_baseline(scenes[0], 5, threads=1, budget_s=20.0)[0]
         emit(out)
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(d, group, np):
+    """--dump-outputs: what the last timed step left for the caller of the step, per image of this rank in batch order --
+    pose parameters (B, 16), loss terms (B, N_LOSS), parameter gradient (B, 16), AdamW moments and step count, flag words
+    and the gradient of every input vertex (Vtot, 3) -- as d/<name>.npy, float32 (integers as float64, exact).  The inputs
+    are the seeded synthetic scenes and the last timed iteration starts from a restart (run_timed), so two runs with the
+    same arguments write the same arrays up to the ~1e-7 float-atomic noise of one backward.  Past DUMP_MAX_BYTES in all,
+    grad_verts_in keeps a fixed, seeded sample of its rows (their indices in grad_verts_rows)."""
+    def cat(name):
+        return np.concatenate([getattr(gb, name).detach().cpu().numpy() for gb in group.batches], 0)
+    arrays = {"params": cat("params"), "losses": cat("losses"), "grad_params": cat("grad_params"), "adam_m": cat("adam_m"),
+              "adam_v": cat("adam_v"), "adam_t": cat("adam_t").astype(np.float64), "flags": cat("flags").astype(np.float64),
+              "grad_verts_in": cat("grad_verts_in")}
+    g = arrays["grad_verts_in"]
+    room = DUMP_MAX_BYTES - sum(a.nbytes for k, a in arrays.items() if k != "grad_verts_in")
+    if g.nbytes > room:
+        rows = np.sort(np.random.default_rng(0).choice(len(g), room // (g[0].nbytes + 8), replace=False))
+        arrays["grad_verts_in"], arrays["grad_verts_rows"] = g[rows], rows.astype(np.float64)
+    os.makedirs(d, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), a)
 
 
 def _r(x, nd=4):

@@ -6,13 +6,13 @@ O=$R/gpurun_out/r04
 mkdir -p $O
 export TMPDIR=/tmp
 cd $R
-timeout 1200 python bench.py > $O/bench_b1.json 2> $O/bench_b1.err
-timeout 600 python bench.py --steps 20 --warmup 5 > $O/bench_driver_invocation.json 2>/dev/null
-timeout 300 python bench.py --no-cpu-baseline --no-extras --steps 200 --warmup 50 --images-per-gpu 8 > $O/bench_b8.json 2>/dev/null
-timeout 300 python bench.py --no-cpu-baseline --no-extras --steps 200 --warmup 50 --images-per-gpu 32 > $O/bench_b32.json 2>/dev/null
+timeout 1200 python bench.py --full > $O/bench_b1.json 2> $O/bench_b1.err
+timeout 600 python bench.py --full --steps 20 --warmup 5 > $O/bench_driver_invocation.json 2>/dev/null
+timeout 300 python bench.py --full --no-cpu-baseline --no-extras --steps 200 --warmup 50 --images-per-gpu 8 > $O/bench_b8.json 2>/dev/null
+timeout 300 python bench.py --full --no-cpu-baseline --no-extras --steps 200 --warmup 50 --images-per-gpu 32 > $O/bench_b32.json 2>/dev/null
 cd /tmp
-B1="python $R/bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-extras"
-NG="python $R/bench.py --steps 20 --warmup 2 --repeats 1 --no-cpu-baseline --no-extras --no-graph"
+B1="python $R/bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --no-extras"
+NG="python $R/bench.py --full --steps 20 --warmup 2 --repeats 1 --no-cpu-baseline --no-extras --no-graph"
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_b1 -- $B1 > /dev/null 2>&1
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_b8 -- $B1 --images-per-gpu 8 --streams 1 > /dev/null 2>&1
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_c1 -- python $R/scripts/run_steps.py --crop hoi --steps 300 > /dev/null 2>&1

@@ -34,10 +34,10 @@ def _env(**kw):
 
 @gpu
 def test_bench_line_n1_and_two_ranks_gloo():
-    """`python bench.py --gpus 1 --steps 20 --warmup 5` and the same workload as
+    """`python bench.py --gpus 1 --steps 20 --warmup 5 --full` and the same workload as
     `torch.distributed.run --nproc-per-node 2 bench.py --gpus 2 ...`: one JSON line each, whole-job value, weak scaling
     (every rank brings its own frame), timings max-reduced over the ranks, metrics vector summed over them."""
-    flags = ["--steps", "20", "--warmup", "5", "--no-extras", "--no-cpu-baseline"]
+    flags = ["--steps", "20", "--warmup", "5", "--no-extras", "--no-cpu-baseline", "--full"]
     r1 = subprocess.run([sys.executable, "bench.py", "--gpus", "1"] + flags, env=_env(), cwd=ROOT, stdout=subprocess.PIPE,
                         stderr=subprocess.PIPE, text=True, timeout=900)
     assert r1.returncode == 0, r1.stderr[-3000:]
@@ -168,3 +168,76 @@ def test_headline_line_stays_under_the_log_tail_with_every_side_record_present()
     out["closeup"] = {"error": "FohoError: " + "y" * 500}
     line = json.dumps(bench.headline(out), separators=(",", ":"))
     assert len(line) < 1900 and "error" in json.loads(line)["roofline"]["secondary"]["closeup"]
+
+
+@gpu
+def test_bench_plain_run_times_exactly_steps_and_dumps_outputs(tmp_path):
+    """The plain form `python bench.py --gpus 1 --steps K --warmup W`: ONE timed region of exactly K iterations, nothing beyond
+    the headline (no roofline, side records or CPU baseline), and --dump-outputs writes what the K-th timed step left as
+    float32 / float64 arrays.  That step starts from a restart of the seeded scene (bench.run_timed), so two runs with the
+    same arguments write the same arrays up to the float-atomic noise of one backward (~1e-7).  K = 30
+    takes 10-iteration graphs: the 29 iterations before the last one end in a 9-iteration graph of their own."""
+    import numpy as np
+
+    def run(steps, warmup, d):
+        r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--dump-outputs", str(d)],
+                           env=_env(), cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        line = _line(r.stdout)
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in line, k
+        assert line["steps"] == steps and line["warmup"] == warmup and line["repeats"] == 1
+        assert "roofline" not in line and "cpu_baseline" not in line and "parity" not in line
+        o = _detail(r.stderr)
+        assert o["repeats"] == 1 and o["metrics"]["n_steps"] == steps and o["nan_images"] == 0
+        assert abs(o["value"] - 1e3 / o["ms_per_step"]) <= 1e-6 * o["value"]
+        assert not {"kernels", "batched", "geo_decode", "cpu_baseline"} & set(o)
+        arrs = {p.stem: np.load(p) for p in d.iterdir()}
+        assert {"params", "losses", "grad_params", "grad_verts_in", "adam_t", "flags"} <= set(arrs)
+        assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+        assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        assert arrs["params"].shape == (1, 16) and arrs["grad_verts_in"].shape[1] == 3
+        assert all(np.isfinite(a).all() for a in arrs.values()) and not arrs["flags"].any()
+        assert arrs["adam_t"].tolist() == [1]              # the last timed step is the first AdamW step after its restart
+        return arrs
+
+    a, b = run(30, 5, tmp_path / "k30a"), run(30, 5, tmp_path / "k30b")
+    for k, x in a.items():
+        assert np.abs(b[k] - x).max() <= 1e-5 * np.abs(x).max(), k
+
+
+def test_dump_outputs_stays_under_its_cap(tmp_path, monkeypatch):
+    """bench.dump_outputs (no GPU needed): every array a float32 / float64 .npy, and past the cap grad_verts_in keeps a fixed,
+    seeded sample of its rows whose indices are written beside it."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+
+    class Batch:
+        def __init__(self, B, V, seed):
+            g = torch.Generator().manual_seed(seed)
+            self.params, self.losses, self.grad_params = torch.rand(B, 16, generator=g), torch.rand(B, 24, generator=g), torch.rand(B, 16, generator=g)
+            self.adam_m, self.adam_v = torch.rand(B, 16, generator=g), torch.rand(B, 16, generator=g)
+            self.adam_t, self.flags = torch.full((B,), 7, dtype=torch.int32), torch.zeros(B, dtype=torch.int32)
+            self.grad_verts_in = torch.rand(V, 3, generator=g)
+
+    class Group:
+        batches = [Batch(2, 30000, 0), Batch(1, 20000, 1)]
+
+    bench.dump_outputs(str(tmp_path / "all"), Group, np)
+    a = {p.stem: np.load(p) for p in (tmp_path / "all").iterdir()}
+    assert a["params"].shape == (3, 16) and a["grad_verts_in"].shape == (50000, 3) and "grad_verts_rows" not in a
+    assert a["adam_t"].dtype == np.float64 and (a["adam_t"] == 7).all()
+    np.testing.assert_array_equal(a["grad_verts_in"][30000:], Group.batches[1].grad_verts_in.numpy())
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 200000)
+    for run in ("s0", "s1"):
+        bench.dump_outputs(str(tmp_path / run), Group, np)
+    s0 = {p.stem: np.load(p) for p in (tmp_path / "s0").iterdir()}
+    s1 = {p.stem: np.load(p) for p in (tmp_path / "s1").iterdir()}
+    assert all(v.dtype in (np.float32, np.float64) for v in s0.values())
+    assert sum(v.nbytes for v in s0.values()) <= 200000 and len(s0["grad_verts_in"]) > 1000
+    rows = s0["grad_verts_rows"].astype(np.int64)
+    np.testing.assert_array_equal(s0["grad_verts_in"], a["grad_verts_in"][rows])
+    for k in s0:
+        np.testing.assert_array_equal(s0[k], s1[k])

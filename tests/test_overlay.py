@@ -1,4 +1,4 @@
-"""Drop-in proof against the reference checkout (build container only: /root/reference does not travel to the GPU box).
+"""Drop-in proof against a FollowMyHold checkout.
 
 Two ways the hot-path modules meet the reference's `foho` package:
   * path overlay -- this repository before the checkout's src/ on sys.path: `pkgutil.extend_path` keeps every module
@@ -6,22 +6,50 @@ Two ways the hot-path modules meet the reference's `foho` package:
     checkout, while foho.guidance.run / foho.alignment.* resolve here;
   * scripts/install_overlay.py -- for the UNCHANGED orchestrator, which puts its own src/ first on every stage's
     PYTHONPATH (src/foho/main.py:19-23): the stage modules are placed inside the checkout.
+
+The checkout is a stand-in built in a temporary directory from what tests/golden/ref_overlay.json recorded of the
+reference (make_overlay_golden.py): its src/foho module layout, where each name `foho.configs` exports lives, the
+orchestrator's PYTHONPATH entry and its own command lines for the three stages.  OptimizationConfig carries the
+reference's values (fixture f7 of ref_meta.json); every other module is a one-line stand-in.
 """
+import json
 import os
-import shutil
 import subprocess
 import sys
 
-import pytest
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
-pytestmark = pytest.mark.skipif(not os.path.isfile(os.path.join(REF, "src", "foho", "main.py")),
-                                reason="reference checkout not mounted")
+GOLD_PATH = os.path.join(ROOT, "tests", "golden", "ref_overlay.json")
+GOLD = json.load(open(GOLD_PATH))
+F7 = json.load(open(os.path.join(ROOT, "tests", "golden", "ref_meta.json")))["f7"]
+
+
+def _checkout(co):
+    """Write a stand-in FollowMyHold checkout at `co`; returns {path relative to src/foho: bytes written}."""
+    names = sorted(GOLD["configs_exports"])
+    special = {
+        "configs/__init__.py": "".join(f"from {GOLD['configs_exports'][n]} import {n}\n" for n in names) + f"__all__ = {names!r}\n",
+        "configs/guid_config.py": ("class OptimizationConfig:\n    def __init__(self):\n"
+                                   + "".join(f"        self.{k} = {v!r}\n" for k, v in F7.items())
+                                   + "\n    def __call__(self):\n        return self\n"),
+        "configs/paths.py": ("import os\n\n\ndef foho_root():\n    return os.path.abspath(os.path.join(os.path.dirname(__file__), "
+                             "'..', '..', '..'))\n\n\ndef third_party_root():\n    return os.path.join(foho_root(), 'third_party')\n"),
+        "configs/pipeline.py": "class PipelineConfig:\n    pass\n\n\ndef load_config(path):\n    raise NotImplementedError(path)\n",
+        "utils/runner.py": "def run_in_conda(*args, **kwargs):\n    raise NotImplementedError\n",
+    }
+    written = {}
+    for rel in GOLD["modules"]:
+        path = os.path.join(co, GOLD["foho_src"], "foho", rel)
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        body = special.get(rel, f'"""Stand-in for foho/{rel} of a FollowMyHold checkout."""\n').encode()
+        with open(path, "wb") as f:
+            f.write(body)
+        written[rel] = body
+    return written
+
 
 CHECK_OVERLAY = r"""
-import os, shlex, sys
-repo, ref = sys.argv[1], sys.argv[2]
+import json, os, shlex, sys
+repo, ref, gold = sys.argv[1], sys.argv[2], json.load(open(sys.argv[3]))
 import foho, foho.guidance.run as G, foho.alignment.h2m as H2M, foho.alignment.mano as MANO, foho.alignment.mesh_align as MA
 for m in (foho, G, H2M, MANO, MA):
     assert os.path.abspath(m.__file__).startswith(repo + os.sep), m.__file__
@@ -32,16 +60,20 @@ from foho.configs import PipelineConfig, load_config, OptimizationConfig, third_
 assert load_config.__module__ == "foho.configs.pipeline" and callable(RUNNER.run_in_conda)
 import foho.hand, foho.preprocess, foho.geometry                     # the reference's other sub-packages stay visible
 assert os.path.abspath(foho.hand.__file__).startswith(ref + os.sep)
-# the orchestrator's own command lines (main.py:229-278) parse with this repository's stage parsers
+# the orchestrator's own command lines (main.py:229-278, recorded by make_overlay_golden.py) parse with this repository's
+# stage parsers
 names = ["project_root", "cropped_obj_img_dir", "mask_dir", "moge_out_dir", "hunyuan_hoi_mesh_dir", "hamer_out_dir",
          "h2m_rt_dir", "aligned_mano_dir", "guidance_out_dir"]
-cmd = MAIN._cmd("foho.guidance.run", {n: f"/data/my dir/{n}" for n in names})
+assert gold["guidance_flags"] == names
+cmd = gold["commands"]["foho.guidance.run"]
 parts = shlex.split(cmd)
 assert parts[:3] == ["python3", "-m", "foho.guidance.run"]
 a = G.build_parser().parse_args(parts[3:])
 assert all(getattr(a, n) == f"/data/my dir/{n}" for n in names) and a.task_list_file is None
 for mod, M in (("foho.alignment.h2m", H2M), ("foho.alignment.mano", MANO)):
-    parts = shlex.split(MAIN._cmd(mod, {n: "/x/" + n for n in M.FLAGS}))
+    assert gold["stage_flags"][mod] == list(M.FLAGS)      # the recorded command carries the flags of this repository's stage
+    parts = shlex.split(gold["commands"][mod])
+    assert parts[:3] == ["python3", "-m", mod]
     a = H2M.build_parser(*M.FLAGS).parse_args(parts[3:])
     assert all(getattr(a, n) == "/x/" + n for n in M.FLAGS)
 print("OVERLAY OK")
@@ -61,21 +93,24 @@ def _clean_env(pythonpath):
     return env
 
 
-def test_path_overlay_keeps_the_reference_packages_visible():
-    out = _run(CHECK_OVERLAY, [ROOT, REF], _clean_env(ROOT + os.pathsep + os.path.join(REF, "src")), cwd="/tmp")
+def test_path_overlay_keeps_the_reference_packages_visible(tmp_path):
+    co = str(tmp_path / "FollowMyHold")
+    _checkout(co)
+    out = _run(CHECK_OVERLAY, [ROOT, co, GOLD_PATH], _clean_env(ROOT + os.pathsep + os.path.join(co, GOLD["foho_src"])),
+               cwd=str(tmp_path))
     assert "OVERLAY OK" in out
 
 
 CHECK_INSTALLED = r"""
 import os, sys
-co, repo = sys.argv[1], sys.argv[2]
+co, repo, stage_path = sys.argv[1], sys.argv[2], sys.argv[3]
 import foho.guidance.run as G, foho.alignment.mesh_align as MA, foho.main as MAIN, followmyhold_amd
 assert os.path.abspath(G.__file__).startswith(co + os.sep) and hasattr(G, "build_parser") and hasattr(G, "_dist_setup")
 assert os.path.abspath(MAIN.__file__).startswith(co + os.sep)
 assert os.path.realpath(followmyhold_amd.__file__).startswith(repo + os.sep)
 from foho.configs import OptimizationConfig
 assert OptimizationConfig.__module__ == "foho.configs.guid_config"      # the checkout's own config drives the kernels
-assert MAIN._foho_src() == os.path.join(co, "src")
+assert os.path.dirname(os.path.dirname(os.path.abspath(MAIN.__file__))) == stage_path     # main.py's _foho_src()
 print("INSTALLED OK")
 """
 
@@ -84,11 +119,12 @@ def test_install_overlay_into_a_checkout(tmp_path):
     """The unchanged orchestrator's stage environment (PYTHONPATH = <checkout>/src only) picks up the HIP-backed stage
     modules after scripts/install_overlay.py; --uninstall restores the checkout byte for byte."""
     co = tmp_path / "FollowMyHold"
-    shutil.copytree(os.path.join(REF, "src", "foho"), co / "src" / "foho", ignore=shutil.ignore_patterns("__pycache__"))
+    originals = _checkout(str(co))
     inst = [sys.executable, os.path.join(ROOT, "scripts", "install_overlay.py"), "--foho-root", str(co)]
     subprocess.run(inst, check=True, stdout=subprocess.PIPE)
-    env = _clean_env(str(co / "src"))                                    # main.py:19-23
-    assert "INSTALLED OK" in _run(CHECK_INSTALLED, [str(co), ROOT], env, cwd=str(tmp_path))
+    stage_path = str(co / GOLD["foho_src"])
+    env = _clean_env(stage_path)                                         # main.py:19-23
+    assert "INSTALLED OK" in _run(CHECK_INSTALLED, [str(co), ROOT, stage_path], env, cwd=str(tmp_path))
     # the stage command exactly as main.py:259-278 spells it, on an empty (but existing) set of directories
     dirs = {}
     for n in ["cropped_obj_img_dir", "mask_dir", "moge_out_dir", "hunyuan_hoi_mesh_dir", "hamer_out_dir", "h2m_rt_dir",
@@ -107,7 +143,6 @@ def test_install_overlay_into_a_checkout(tmp_path):
     assert r.returncode == 0 and "No Hunyuan HOI meshes found" in r.stdout, r.stdout[-2000:]
     subprocess.run(inst + ["--uninstall"], check=True, stdout=subprocess.PIPE)
     for rel in ["guidance/run.py", "alignment/h2m.py", "alignment/mano.py", "alignment/mesh_align.py"]:
-        a = open(os.path.join(REF, "src", "foho", rel), "rb").read()
-        assert open(co / "src" / "foho" / rel, "rb").read() == a
+        assert open(co / "src" / "foho" / rel, "rb").read() == originals[rel]
     assert not os.path.lexists(co / "src" / "followmyhold_amd")
     assert not [f for f in os.listdir(co / "src" / "foho" / "guidance") if f.endswith(".reference")]
