@@ -98,6 +98,51 @@ def latent2sdf(pred, xyz_samples, grid_size, vae, device, num_chunks=8000):
     return -grid_logits.view((1, grid_size[0], grid_size[1], grid_size[2])).float()
 
 
+
+FINAL_DECODES = ("dense", "hierarchical")
+
+
+def final_decode_mode(mode=None):
+    """The final decode's mode: `mode`, else $FOHO_FINAL_DECODE, else "dense" (volume.py: "hierarchical" queries the grid only near
+    the surface, with a mesh identical to the dense one's for every surface the coarse level sees)."""
+    mode = mode if mode is not None else (os.environ.get("FOHO_FINAL_DECODE") or "dense")
+    if mode not in FINAL_DECODES:
+        raise E.L.FohoError(f"final_decode {mode!r}: one of {FINAL_DECODES}")
+    return mode
+
+
+def _require_hip_geo(vae):
+    hip = getattr(vae, "hip_geo", None)
+    if hip is None:
+        raise E.L.FohoError("hierarchical final decode: needs vae.hip_geo, the HIP geometry decoder (geo_decode.install(vae)); the torch module's "
+                            "outputs depend on the batch shape, so decoded subsets would not equal the dense decode")
+    return hip
+
+
+def sdf_hierarchical_from_tokens(tokens, bmin, bmax, res, hip, min_res=None, band=1):
+    """The hierarchical decode of one image's VAE tokens (1, L, width) -> ((1, G, G, G) float32 negated logits, stats).  Every query
+    goes through `hip(queries, tokens)` exactly as latent2sdf's dense call does: K / V prepared once for the tokens, the logits in
+    the tokens' dtype -- so the decoded values equal the dense decode's bit for bit."""
+    from . import volume
+    res = int(res)
+    G = res + 1
+    with torch.no_grad():
+        logits, stats = volume.hierarchical_grid_logits(lambda q: hip(q.reshape(1, -1, 3), tokens).reshape(-1).float(), bmin, bmax, res,
+                                                        min_res=min_res, band=band, device=hip.device)
+    return -logits.view(1, G, G, G), stats
+
+
+def latent2sdf_hierarchical(pred, bmin, bmax, res, vae, device, min_res=None, band=1):
+    """latent2sdf with the hierarchical decode (volume.hierarchical_grid_logits) on the (res+1)^3 grid over [bmin, bmax]: the tokens
+    once, as latent2sdf computes them, then the HIP geometry decoder on the gathered query points of each level.
+    -> ((1, G, G, G) float32, negative inside, stats).  Requires `vae.hip_geo`."""
+    from . import volume
+    volume.check_levels(res, min_res)
+    hip = _require_hip_geo(vae)
+    pred = vae_tokens(vae, 1 / vae.scale_factor * pred)
+    return sdf_hierarchical_from_tokens(pred, bmin, bmax, res, hip, min_res=min_res, band=band)
+
+
 def _bound_active_rows(vae, n_rows):
     """The decoder's active-row backward (foho_geo_decode_bwd_rows) launches row blocks up to an upper bound of the rows that carry a
     gradient; every block beyond the actual count is fourteen empty launches (4.5 us each).  In the guidance loop the gradient comes
@@ -234,7 +279,8 @@ class GuidedShapePipeline:
     # ------------------------------------------------------------------ B images through one pass of the schedule
     @torch.no_grad()
     def call_batch(self, images, paths, generators=None, guidance_scale=7.5, num_chunks=8000, config=None, renderer=None,
-                   J_regressor=None, guidance_octree_resolution=64, final_octree_resolution=384, obj_capacity=None, fovs=None):
+                   J_regressor=None, guidance_octree_resolution=64, final_octree_resolution=384, obj_capacity=None, fovs=None,
+                   final_decode=None, final_decode_min_res=None):
         """`__call__` for B images at once ("within a GPU, batch the rank's images through each kernel
         launch").  The reference runs its images one after the other (RUN:208-259, batch_size = 1, guid_config.py:9); here
         one pass of the 20-step schedule serves all of them: the DiT and the ShapeVAE transformer run on B latents, the
@@ -252,8 +298,16 @@ class GuidedShapePipeline:
         step for its noise prediction, none for its pose (PL:1394-1397, 1511-1513; `stats["skipped_empty"]`); an image whose
         surface is not a closed manifold or exceeds the capacity, or whose loss is NaN (PL:1442-1444, 1590-1592), LEAVES the batch:
         its slot is frozen, the other images carry on, and its entry of the result list is a `BatchLeftFastPath` instance -- the
-        caller re-runs that image through `__call__`, which handles all of these the reference's way."""
+        caller re-runs that image through `__call__`, which handles all of these the reference's way.
+
+        final_decode: "dense" or "hierarchical" (None: $FOHO_FINAL_DECODE, else "dense"), with final_decode_min_res, as in `__call__`: the
+        last step's grid of each image decoded densely or near the surface only (volume.py); per-image stats in stats["final_decode"]."""
         B = len(images)
+        final_mode = final_decode_mode(final_decode)
+        if final_mode == "hierarchical":
+            from . import volume
+            volume.check_levels(final_octree_resolution, final_decode_min_res)
+            _require_hip_geo(self.vae)
         device, dtype = self.device, self.dtype
         cfg0 = config() if config is not None else E.OptimizationConfig()
         self.stats = stats = {"inner_iterations": 0, "images": B, "skipped_empty": 0}
@@ -311,6 +365,20 @@ class GuidedShapePipeline:
                     continue
                 logits = [self.vae.geo_decoder(xyz[s0:s0 + num_chunks].half().unsqueeze(0), pred[b:b + 1]) for s0 in range(0, xyz.shape[0], num_chunks)]
                 out.append(-torch.cat(logits, dim=1).view(-1).float())
+            return torch.stack(out, 0)
+
+        def final_sdf_hierarchical(x1, res):
+            """sdf_of's fields for the final step by the hierarchical decode: the VAE transformer on all images as sdf_of runs it, the
+            decoder near each image's surface only (volume.py)."""
+            pred = vae_tokens(self.vae, 1 / self.vae.scale_factor * x1)
+            out, stats["final_decode"] = [], [None] * B
+            for b in range(B):
+                if b in left:
+                    out.append(torch.ones((res + 1) ** 3, device=device))
+                    continue
+                sdf_b, stats["final_decode"][b] = sdf_hierarchical_from_tokens(pred[b:b + 1], bmin, bmax, res, hip_dec,
+                                                                                min_res=final_decode_min_res)
+                out.append(sdf_b.view(-1))
             return torch.stack(out, 0)
 
         LEAVE, EMPTY = 1 | 16 | 32, 64      # flag bits: NaN loss, capacity overflow, not a closed manifold | empty iso-surface
@@ -403,7 +471,10 @@ class GuidedShapePipeline:
             # only matter as the fall-back of a later empty decode, so they are taken on the guidance grid
             res = final_octree_resolution if i == n_steps - 1 else guid_res
             xyz_d, gsz_d = grid(res) if res != guid_res else (xyz_samples, grid_size)
-            sdf = sdf_of(self.scheduler.step_final(noise_pred, t, latents), xyz_d, gsz_d)
+            if i == n_steps - 1 and final_mode == "hierarchical":
+                sdf = final_sdf_hierarchical(self.scheduler.step_final(noise_pred, t, latents), res)
+            else:
+                sdf = sdf_of(self.scheduler.step_final(noise_pred, t, latents), xyz_d, gsz_d)
             for b in range(B):
                 if b in left:
                     continue
@@ -440,6 +511,13 @@ class GuidedShapePipeline:
         kwargs.pop("callback", None)            # popped and ignored, as in PL:1073-1074
         kwargs.pop("callback_steps", None)
         final_res = int(kwargs.pop("final_octree_resolution", 384))          # PL:1627 (tests use a smaller grid)
+        # "dense" (default) | "hierarchical": how the final-step grid is decoded (volume.py); not in the signature, which is the reference's
+        final_mode = final_decode_mode(kwargs.pop("final_decode", None))
+        final_min_res = kwargs.pop("final_decode_min_res", None)
+        if final_mode == "hierarchical":                  # refused before any work, not after the whole schedule
+            from . import volume
+            volume.check_levels(final_res, final_min_res)
+            _require_hip_geo(self.vae)
         J_regressor = kwargs.pop("J_regressor", None)                        # default: the file of PL:1218
         on_phase_end = kwargs.pop("on_phase_end", None)      # hook(phase, denoising step, GuidanceBatch): inspection / tests
         self.stats = stats = {"inner_iterations": 0, "skipped_empty": 0}
@@ -506,9 +584,12 @@ class GuidedShapePipeline:
         hand_moge = torch.as_tensor(scene["hand_verts"], dtype=torch.float32, device=device)
         hand_faces = torch.as_tensor(scene["hand_faces"], dtype=torch.int64, device=device)
 
-        def decode_mesh(noise_pred, t, latents, res, xyz, gsz):
+        def decode_mesh(noise_pred, t, latents, res, xyz, gsz, hierarchical=False):
             x1 = self.scheduler.step_final(noise_pred, t, latents)
-            sdf = latent2sdf(x1, xyz, gsz, self.vae, device, num_chunks)
+            if hierarchical:          # the final step's grid queried near the surface only; FlexiCubes still on the dense grid
+                sdf, stats["final_decode"] = latent2sdf_hierarchical(x1, bmin, bmax, res, self.vae, device, min_res=final_min_res)
+            else:
+                sdf = latent2sdf(x1, xyz, gsz, self.vae, device, num_chunks)
             return ops.flexicubes(xyz, sdf[0].flatten(), res)
 
         # Phases B and C re-extract the object from the latent in every iteration (PL:1391-1393, 1507-1509): vertex count,
@@ -676,7 +757,8 @@ class GuidedShapePipeline:
                 xyz_np, grid_size, _ = generate_dense_grid_points(bmin, bmax, octree_depth=5, octree_resolution=octree_res,
                                                                   indexing="ij")
                 xyz_samples = torch.as_tensor(xyz_np, dtype=torch.float32, device=device)
-            verts, faces, _ = decode_mesh(noise_pred_obj, t, obj_latents, octree_res, xyz_samples, grid_size)
+            verts, faces, _ = decode_mesh(noise_pred_obj, t, obj_latents, octree_res, xyz_samples, grid_size,
+                                          hierarchical=final_mode == "hierarchical" and i == num_inference_steps - 1)
             if verts.shape[0] == 0:
                 print("Invalid mesh detected, aborting step!")
                 continue
