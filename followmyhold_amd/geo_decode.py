@@ -411,6 +411,48 @@ class _GeoDecodeFn(torch.autograd.Function):
         return ctx.dec.decode_bwd(queries, grad, saved[0] if saved else None).to(kv.dtype), None, None
 
 
+class _GeoBandFn(torch.autograd.Function):
+    """The band decode of B images' grids (volume.hierarchical_grid_logits_batch) with the gradient to each image's K / V.
+
+    forward(queries, dec, run, dtype, *kvs): `run(decodes)` runs the band decode with decodes[b] = image b's rows through
+    foho_geo_decode_fwd against kvs[b] (installed by set_kv whenever the workspace holds another image's), rounded to `dtype` like the
+    dense route's output -> (B, N) float32 fields.  backward: exactly _GeoDecodeFn's, per image, on the FULL query tensor `queries`
+    (dec.grid_queries of the grid) and the full incoming gradient -- it recomputes every row it needs and never reads a forward value,
+    so the gradient is bitwise the dense route's for the same incoming gradient.  "keep" keeps activations of every forward row and
+    cannot serve a band decode: refused."""
+
+    @staticmethod
+    def forward(ctx, queries, dec, run, dtype, *kvs):
+        if dec.backward_mode not in ("rows", "recompute"):
+            raise L.FohoError(f"band decode: HipGeoDecoder.backward_mode {dec.backward_mode!r} is not supported ('rows' or 'recompute'; "
+                              "'keep' keeps the activations of every forward row)")
+        held = [None, None]                # (image whose K / V the workspace holds, its epoch)
+
+        def decode_of(b):
+            def decode(p):
+                if held[0] != b or held[1] != dec._ws_epoch:
+                    dec.set_kv(kvs[b])
+                    held[:] = [b, dec._ws_epoch]
+                return dec.decode(p).to(dtype).float()
+            return decode
+
+        fields = run([decode_of(b) for b in range(len(kvs))])
+        ctx.dec, ctx.mode, ctx.held = dec, dec.backward_mode, tuple(held)
+        ctx.save_for_backward(queries, *[kv.detach() for kv in kvs])
+        return torch.stack(fields)
+
+    @staticmethod
+    def backward(ctx, grad):
+        queries, *kvs = ctx.saved_tensors
+        dec, out = ctx.dec, []
+        for b, kv in enumerate(kvs):
+            if (b, dec._ws_epoch) != ctx.held:
+                dec.set_kv(kv)
+            g = dec.decode_bwd_rows(queries, grad[b]) if ctx.mode == "rows" else dec.decode_bwd(queries, grad[b])
+            out.append(g.to(kv.dtype))
+        return (None, None, None, None, *out)
+
+
 def install(vae, device="cuda", chunk_rows=None):
     """Attach a HipGeoDecoder built from `vae.geo_decoder` as `vae.hip_geo`: `pipeline.latent2sdf` then decodes with it,
     with or without gradients to the latent.  Raises when the decoder's shape is outside what the kernels take."""

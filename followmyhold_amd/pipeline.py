@@ -143,6 +143,95 @@ def latent2sdf_hierarchical(pred, bmin, bmax, res, vae, device, min_res=None, ba
     return sdf_hierarchical_from_tokens(pred, bmin, bmax, res, hip, min_res=min_res, band=band)
 
 
+GUIDANCE_DECODES = ("dense", "hierarchical")
+
+
+def guidance_decode_mode(mode=None):
+    """How the guidance grid is decoded -- the in-loop decodes of phases B / C and the per-step decodes before the last step: `mode`,
+    else $FOHO_GUIDANCE_DECODE, else "dense".  "hierarchical" is the band decode of latent2sdf_band."""
+    mode = mode if mode is not None else (os.environ.get("FOHO_GUIDANCE_DECODE") or "dense")
+    if mode not in GUIDANCE_DECODES:
+        raise E.L.FohoError(f"guidance_decode {mode!r}: one of {GUIDANCE_DECODES}")
+    return mode
+
+
+def guidance_levels(res, min_res=None):
+    """(res, min_res) of the guidance grid's band decode after volume.check_levels.  min_res defaults to res / 2 (33^3 at level 0 of
+    the 65^3 grid), not the final decode's res / 4: a surface component inside one-sign coarse cells is missed, and in the loop that
+    changes the losses -- a 17^3 level 0 has 0.1375-unit cells, wide enough to hide a mug handle."""
+    from . import volume
+    res = int(res)
+    return volume.check_levels(res, res // 2 if min_res is None else min_res)
+
+
+def _require_band_decoder(vae):
+    hip = getattr(vae, "hip_geo", None)
+    if hip is None:
+        raise E.L.FohoError("hierarchical guidance decode: needs vae.hip_geo, the HIP geometry decoder (geo_decode.install(vae)); the torch "
+                            "module's outputs depend on the batch shape, so decoded subsets would not equal the dense decode")
+    if hip.backward_mode == "keep":
+        raise E.L.FohoError("hierarchical guidance decode: vae.hip_geo.backward_mode 'keep' keeps the activations of every forward row and "
+                            "cannot serve a band decode: use 'rows' (the default) or 'recompute'")
+    return hip
+
+
+def sdf_band_from_tokens(tokens, xyz_samples, res, hip, bmin, bmax, min_res=None, band=1):
+    """The band decode of B images' VAE tokens (a list of (1, L, width) tensors) on the grid `xyz_samples` of resolution `res` over
+    [bmin, bmax] -> ((B, (res+1)^3) float32 negated logits, list of B stats, host reads).  The images step through the levels in
+    lockstep with one host read per level and per closure round (volume.hierarchical_grid_logits_batch).
+
+    Under autograd (a token tensor that requires grad) the decode is geo_decode._GeoBandFn on each image's `hip.kv_of(tokens)`: the
+    logits' gradient reaches the tokens through the dense route's backward on the full grid, bitwise the dense route's for the same
+    incoming gradient.  Without it every query goes through `hip(queries, tokens)` as latent2sdf's no-gradient call does.  Either way
+    a decoded value equals the dense route's bit for bit, and the field is the dense one's everywhere FlexiCubes reads a value."""
+    from . import geo_decode, volume
+    res, min_res = guidance_levels(res, min_res)
+    n = (res + 1) ** 3
+    if xyz_samples.shape[0] != n:
+        raise E.L.FohoError(f"band decode: {xyz_samples.shape[0]} grid points, a grid of resolution {res} has {n}")
+    if not tokens:
+        return torch.empty(0, n, device=hip.device), [], 0
+    dtype = tokens[0].dtype
+    box = {}
+
+    def run(decodes):
+        fields, box["stats"], box["reads"] = volume.hierarchical_grid_logits_batch(decodes, bmin, bmax, res, min_res=min_res, band=band,
+                                                                                   device=hip.device)
+        return fields
+
+    queries = hip.grid_queries(xyz_samples)          # the dense route's query tensor: what the backward runs on
+    if torch.is_grad_enabled() and any(t.requires_grad for t in tokens):      # _GeoBandFn refuses backward_mode "keep"
+        logits = geo_decode._GeoBandFn.apply(queries, hip, run, dtype, *[hip.kv_of(t) for t in tokens])
+    else:
+        with torch.no_grad():
+            logits = torch.stack(run([lambda p, t=t: hip(p.reshape(1, -1, 3), t).reshape(-1).float() for t in tokens]))
+    return (-logits.to(dtype)).float(), box["stats"], box["reads"]
+
+
+def latent2sdf_band(pred, xyz_samples, grid_size, vae, device, bmin, bmax, min_res=None, band=1):
+    """latent2sdf with the band decode (volume.hierarchical_grid_logits), with or without gradient: the tokens once, as latent2sdf
+    computes them, then the HIP geometry decoder on each level's gathered points of the grid `xyz_samples` over [bmin, bmax].
+    -> ((1, G, G, G) float32, negative inside, stats).  Requires `vae.hip_geo` in backward_mode "rows" or "recompute".
+
+    The one behavioural difference from latent2sdf: a NaN that the decoder would produce only at points the band fills is not seen."""
+    G = int(grid_size[0])
+    guidance_levels(G - 1, min_res)
+    hip = _require_band_decoder(vae)
+    pred = vae_tokens(vae, 1 / vae.scale_factor * pred)
+    sdf, stats, _ = sdf_band_from_tokens([pred], xyz_samples, G - 1, hip, bmin, bmax, min_res=min_res, band=band)
+    return sdf.view(1, G, G, G), stats[0]
+
+
+def _tally(entry, st):
+    """Add one band decode's stats to stats["guidance_decode"] (one image's entry)."""
+    n = entry.get("decodes", 0)
+    entry.update(decodes=n + 1, levels=st["levels"],
+                 mean_decoded_fraction=(entry.get("mean_decoded_fraction", 0.0) * n + st["decoded_fraction"]) / (n + 1),
+                 max_decoded_fraction=max(entry.get("max_decoded_fraction", 0.0), st["decoded_fraction"]),
+                 max_closure_rounds=max(entry.get("max_closure_rounds", 0), st["closure_rounds"]),
+                 fallbacks=entry.get("fallbacks", 0) + int(st["fallback"]))
+
+
 def _bound_active_rows(vae, n_rows):
     """The decoder's active-row backward (foho_geo_decode_bwd_rows) launches row blocks up to an upper bound of the rows that carry a
     gradient; every block beyond the actual count is fourteen empty launches (4.5 us each).  In the guidance loop the gradient comes
@@ -280,7 +369,7 @@ class GuidedShapePipeline:
     @torch.no_grad()
     def call_batch(self, images, paths, generators=None, guidance_scale=7.5, num_chunks=8000, config=None, renderer=None,
                    J_regressor=None, guidance_octree_resolution=64, final_octree_resolution=384, obj_capacity=None, fovs=None,
-                   final_decode=None, final_decode_min_res=None):
+                   final_decode=None, final_decode_min_res=None, guidance_decode=None, guidance_decode_min_res=None):
         """`__call__` for B images at once ("within a GPU, batch the rank's images through each kernel
         launch").  The reference runs its images one after the other (RUN:208-259, batch_size = 1, guid_config.py:9); here
         one pass of the 20-step schedule serves all of them: the DiT and the ShapeVAE transformer run on B latents, the
@@ -301,16 +390,25 @@ class GuidedShapePipeline:
         caller re-runs that image through `__call__`, which handles all of these the reference's way.
 
         final_decode: "dense" or "hierarchical" (None: $FOHO_FINAL_DECODE, else "dense"), with final_decode_min_res, as in `__call__`: the
-        last step's grid of each image decoded densely or near the surface only (volume.py); per-image stats in stats["final_decode"]."""
+        last step's grid of each image decoded densely or near the surface only (volume.py); per-image stats in stats["final_decode"].
+        guidance_decode: "dense" or "hierarchical" (None: $FOHO_GUIDANCE_DECODE, else "dense"), with guidance_decode_min_res, as in
+        `__call__`: every decode on the guidance grid by the band decode, all images in lockstep (sdf_band_from_tokens); per-image stats
+        in stats["guidance_decode"]."""
         B = len(images)
         final_mode = final_decode_mode(final_decode)
         if final_mode == "hierarchical":
             from . import volume
             volume.check_levels(final_octree_resolution, final_decode_min_res)
             _require_hip_geo(self.vae)
+        guid_band = guidance_decode_mode(guidance_decode) == "hierarchical"
+        if guid_band:
+            guidance_levels(guidance_octree_resolution, guidance_decode_min_res)
+            _require_band_decoder(self.vae)
         device, dtype = self.device, self.dtype
         cfg0 = config() if config is not None else E.OptimizationConfig()
         self.stats = stats = {"inner_iterations": 0, "images": B, "skipped_empty": 0}
+        if guid_band:
+            stats["guidance_decode"] = [{} for _ in range(B)]
         left = {}                 # image -> BatchLeftFastPath: frozen slots
         do_cfg = guidance_scale >= 0 and not (getattr(self.model, "guidance_embed", False) is True)
         img, msk = self.prepare_image(list(images))
@@ -367,6 +465,19 @@ class GuidedShapePipeline:
                 out.append(-torch.cat(logits, dim=1).view(-1).float())
             return torch.stack(out, 0)
 
+        def sdf_band_of(x1):
+            """sdf_of on the guidance grid by the band decode: the VAE transformer on all images as sdf_of runs it, the images that are
+            still in the batch through the levels in lockstep."""
+            pred = vae_tokens(self.vae, 1 / self.vae.scale_factor * x1)
+            live = [b for b in range(x1.shape[0]) if b not in left]
+            out = [torch.ones(xyz_samples.shape[0], device=device) for _ in range(x1.shape[0])]
+            sdf, sts, _ = sdf_band_from_tokens([pred[b:b + 1] for b in live], xyz_samples, guid_res, hip_dec, bmin, bmax,
+                                               min_res=guidance_decode_min_res)
+            for j, b in enumerate(live):
+                out[b] = sdf[j]
+                _tally(stats["guidance_decode"][b], sts[j])
+            return torch.stack(out, 0)
+
         def final_sdf_hierarchical(x1, res):
             """sdf_of's fields for the final step by the hierarchical decode: the VAE transformer on all images as sdf_of runs it, the
             decoder near each image's surface only (volume.py)."""
@@ -403,7 +514,7 @@ class GuidedShapePipeline:
             for k in range(int(iters)):
                 opt.zero_grad(set_to_none=True)
                 x1 = self.scheduler.step_final(torch.cat(noise, 0), t, latents)
-                sdf = sdf_of(x1, xyz_samples, grid_size)
+                sdf = sdf_band_of(x1) if guid_band else sdf_of(x1, xyz_samples, grid_size)
                 loss = fobj(sdf, cfg)                                   # (B,): one replay for all images
                 fl = gb.flags.cpu().tolist()                            # the iteration's read-back (NaN is bit 0 of the flags) ...
                 if hip_dec is not None:                                 # ... with the rows the decoder's backward will find a gradient on
@@ -473,6 +584,8 @@ class GuidedShapePipeline:
             xyz_d, gsz_d = grid(res) if res != guid_res else (xyz_samples, grid_size)
             if i == n_steps - 1 and final_mode == "hierarchical":
                 sdf = final_sdf_hierarchical(self.scheduler.step_final(noise_pred, t, latents), res)
+            elif i < n_steps - 1 and guid_band:
+                sdf = sdf_band_of(self.scheduler.step_final(noise_pred, t, latents))
             else:
                 sdf = sdf_of(self.scheduler.step_final(noise_pred, t, latents), xyz_d, gsz_d)
             for b in range(B):
@@ -518,9 +631,18 @@ class GuidedShapePipeline:
             from . import volume
             volume.check_levels(final_res, final_min_res)
             _require_hip_geo(self.vae)
+        # "dense" (default) | "hierarchical": how the guidance grid is decoded (latent2sdf_band), with guidance_decode_min_res; not in the
+        # signature either
+        guid_band = guidance_decode_mode(kwargs.pop("guidance_decode", None)) == "hierarchical"
+        guid_min_res = kwargs.pop("guidance_decode_min_res", None)
+        if guid_band:
+            guidance_levels(kwargs.get("guidance_octree_resolution", 64), guid_min_res)
+            _require_band_decoder(self.vae)
         J_regressor = kwargs.pop("J_regressor", None)                        # default: the file of PL:1218
         on_phase_end = kwargs.pop("on_phase_end", None)      # hook(phase, denoising step, GuidanceBatch): inspection / tests
         self.stats = stats = {"inner_iterations": 0, "skipped_empty": 0}
+        if guid_band:
+            stats["guidance_decode"] = {}
         self.loss_log = loss_log = []        # (phase, denoising step, iteration, loss terms) every 10th iteration, like the prints
         self.param_log = param_log = []      # (phase, denoising step, the 16 similarity parameters, noise prediction) at phase end
         device, dtype = self.device, self.dtype
@@ -584,10 +706,20 @@ class GuidedShapePipeline:
         hand_moge = torch.as_tensor(scene["hand_verts"], dtype=torch.float32, device=device)
         hand_faces = torch.as_tensor(scene["hand_faces"], dtype=torch.int64, device=device)
 
-        def decode_mesh(noise_pred, t, latents, res, xyz, gsz, hierarchical=False):
+        def guidance_sdf(x1):
+            """latent2sdf on the guidance grid, by the band decode when guidance_decode is "hierarchical"."""
+            if not guid_band:
+                return latent2sdf(x1, xyz_samples, grid_size, self.vae, device, num_chunks)
+            sdf, st = latent2sdf_band(x1, xyz_samples, grid_size, self.vae, device, bmin, bmax, min_res=guid_min_res)
+            _tally(stats["guidance_decode"], st)
+            return sdf
+
+        def decode_mesh(noise_pred, t, latents, res, xyz, gsz, hierarchical=False, band=False):
             x1 = self.scheduler.step_final(noise_pred, t, latents)
             if hierarchical:          # the final step's grid queried near the surface only; FlexiCubes still on the dense grid
                 sdf, stats["final_decode"] = latent2sdf_hierarchical(x1, bmin, bmax, res, self.vae, device, min_res=final_min_res)
+            elif band:                # a step before the last on the guidance grid
+                sdf = guidance_sdf(x1)
             else:
                 sdf = latent2sdf(x1, xyz, gsz, self.vae, device, num_chunks)
             return ops.flexicubes(xyz, sdf[0].flatten(), res)
@@ -631,7 +763,7 @@ class GuidedShapePipeline:
             for k in range(int(iters)):
                 opt.zero_grad()
                 x1 = self.scheduler.step_final(noise_pred, t, obj_latents)
-                sdf = latent2sdf(x1, xyz_samples, grid_size, self.vae, device, num_chunks)[0].flatten()
+                sdf = guidance_sdf(x1)[0].flatten()
                 loss, cur = None, gb
                 if use_fast:
                     g2, fobj = fast_objective(cap)
@@ -758,7 +890,8 @@ class GuidedShapePipeline:
                                                                   indexing="ij")
                 xyz_samples = torch.as_tensor(xyz_np, dtype=torch.float32, device=device)
             verts, faces, _ = decode_mesh(noise_pred_obj, t, obj_latents, octree_res, xyz_samples, grid_size,
-                                          hierarchical=final_mode == "hierarchical" and i == num_inference_steps - 1)
+                                          hierarchical=final_mode == "hierarchical" and i == num_inference_steps - 1,
+                                          band=guid_band and i < num_inference_steps - 1)
             if verts.shape[0] == 0:
                 print("Invalid mesh detected, aborting step!")
                 continue

@@ -17,6 +17,9 @@ Known limit: a surface component lying entirely inside cells that the coarse lev
 hierarchical decoding has the same limit).  That is why the mode is opt-in and the dense decode stays the default.
 
 The kernels are libfoho_vol.so's (csrc/foho_vol.hip, C ABI csrc/foho_vol.h): mark, select, close, count, emit, fill, scatter.
+The guidance loop's band decode (pipeline.latent2sdf_band) runs the same scheme on the 65^3 grid, for several
+images in lockstep through hierarchical_grid_logits_batch.
+
 There is no CPU path: the binding raises when the library is missing or of another version.
 """
 import ctypes
@@ -93,24 +96,44 @@ def axis_tables(bmin, bmax, res):
 
 
 class _Compactor:
-    """Point mask -> (ascending int32 indices, fp16-rounded xyz): foho_vol_count, one read-back of the count, foho_vol_emit."""
+    """Point masks of several images -> per image (ascending int32 indices, fp16-rounded xyz): foho_vol_count per image into its own
+    slot of one int32[B] tensor, ONE read-back of all the counts, foho_vol_emit per image.  `reads` counts the read-backs."""
 
-    def __init__(self, tables, res, device):
+    def __init__(self, tables, res, n_images, device):
         self.tables, self.res, self.device = tables, res, device
-        self.total = torch.zeros(1, dtype=torch.int32, device=device)
+        self.totals = torch.zeros(max(int(n_images), 1), dtype=torch.int32, device=device)
+        self.reads = 0
 
-    def __call__(self, sel, r):
+    def __call__(self, sels, r):
+        """sels: {image: point mask over the (r+1)^3 points of level r} -> {image: (idx, xyz)}."""
         L = lib()
         n_points = (r + 1) ** 3
-        boff = torch.empty(int(L.foho_vol_count_blocks(n_points)), dtype=torch.int32, device=self.device)
+        nb = int(L.foho_vol_count_blocks(n_points))
         st = _stream(self.device)
-        _check(L.foho_vol_count(_p(sel), n_points, _p(boff), _p(self.total), st), "foho_vol_count")
-        n = int(self.total.item())
-        idx = torch.empty(n, dtype=torch.int32, device=self.device)
-        xyz = torch.empty(n, 3, dtype=torch.float32, device=self.device)
-        if n:
-            _check(L.foho_vol_emit(_p(sel), r, self.res, _p(self.tables), _p(boff), _p(idx), _p(xyz), st), "foho_vol_emit")
-        return idx, xyz
+        boff = {}
+        for b, sel in sels.items():
+            boff[b] = torch.empty(nb, dtype=torch.int32, device=self.device)
+            _check(L.foho_vol_count(_p(sel), n_points, _p(boff[b]), _p(self.totals[b:b + 1]), st), "foho_vol_count")
+        if not sels:
+            return {}
+        counts = self.totals.tolist()
+        self.reads += 1
+        out = {}
+        for b, sel in sels.items():
+            n = int(counts[b])
+            idx = torch.empty(n, dtype=torch.int32, device=self.device)
+            xyz = torch.empty(n, 3, dtype=torch.float32, device=self.device)
+            if n:
+                _check(L.foho_vol_emit(_p(sel), r, self.res, _p(self.tables), _p(boff[b]), _p(idx), _p(xyz), st), "foho_vol_emit")
+            out[b] = (idx, xyz)
+        return out
+
+
+def _decoded(decode, xyz, n):
+    vals = decode(xyz).reshape(-1).to(torch.float32).contiguous() if n else xyz.new_empty(0)
+    if vals.numel() != n:
+        raise FohoError(f"hierarchical decode: the decoder returned {vals.numel()} values for {n} points")
+    return vals
 
 
 def hierarchical_grid_logits(decode, bmin, bmax, res, min_res=None, band=1, max_rounds=8, device=None):
@@ -120,70 +143,91 @@ def hierarchical_grid_logits(decode, bmin, bmax, res, min_res=None, band=1, max_
     those points; every other point carries a fill value of the right sign (see the module's docstring for the contract and its
     limit).  stats: levels, decoded per level, closure rounds and the points each decoded, total decoded, decoded fraction,
     fallback."""
+    fields, stats, _ = hierarchical_grid_logits_batch([decode], bmin, bmax, res, min_res=min_res, band=band, max_rounds=max_rounds,
+                                                      device=device)
+    return fields[0], stats[0]
+
+
+def hierarchical_grid_logits_batch(decodes, bmin, bmax, res, min_res=None, band=1, max_rounds=8, device=None):
+    """hierarchical_grid_logits for B images in lockstep: decodes[b] is image b's decode callable.  Every level and every closure round
+    reads the point counts of all images back at once (one host read each, not one per image); an image whose closure has settled
+    decodes nothing in later rounds.  Each image's kernels and decoder calls are the ones its own hierarchical_grid_logits makes, in
+    the same order, so its field and stats are the same.
+
+    -> (list of B fields, list of B stats, host reads)."""
     res, min_res = check_levels(res, min_res)
     band, max_rounds = int(band), int(max_rounds)
     if band < 0 or max_rounds < 0:
         raise FohoError(f"hierarchical decode: band {band} and max_rounds {max_rounds} must be >= 0")
     device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    B = len(decodes)
+    imgs = range(B)
     L = lib()
     st = _stream(device)
     tables = axis_tables(bmin, bmax, res).to(device)
-    emit = _Compactor(tables, res, device)
+    emit = _Compactor(tables, res, B, device)
 
-    def run(sel, r):
-        idx, xyz = emit(sel, r)
-        vals = decode(xyz).reshape(-1).to(torch.float32).contiguous() if idx.numel() else idx.float()
-        if vals.numel() != idx.numel():
-            raise FohoError(f"hierarchical decode: the decoder returned {vals.numel()} values for {idx.numel()} points")
-        return idx, vals
-
-    # level 0: the dense (min_res+1)^3 grid
+    # level 0: the dense (min_res+1)^3 grid -- the same points for every image
     r = min_res
-    dec = _mask((r + 1) ** 3, device, -1)
-    idx, vals = run(_mask((r + 1) ** 3, device, -1), r)
-    field = torch.empty((r + 1) ** 3, dtype=torch.float32, device=device)
-    _check(L.foho_vol_scatter(_p(idx), _p(vals), idx.numel(), _p(field), st), "foho_vol_scatter")
-    stats = {"levels": [r], "decoded_per_level": [int(idx.numel())]}
+    dec = [_mask((r + 1) ** 3, device, -1) for _ in imgs]
+    idx, xyz = emit({0: _mask((r + 1) ** 3, device, -1)}, r)[0] if B else (None, None)
+    field, stats = [], []
+    for b in imgs:
+        vals = _decoded(decodes[b], xyz, idx.numel())
+        field.append(torch.empty((r + 1) ** 3, dtype=torch.float32, device=device))
+        _check(L.foho_vol_scatter(_p(idx), _p(vals), idx.numel(), _p(field[b]), st), "foho_vol_scatter")
+        stats.append({"levels": [r], "decoded_per_level": [int(idx.numel())]})
     # levels 1..L: points inside active coarse cells
     while r < res:
-        cells = r ** 3
-        mixed, active = _mask(cells, device), _mask(cells, device)
-        _check(L.foho_vol_mark(_p(field), r, band, _p(mixed), _p(active), st), "foho_vol_mark")
-        n_fine = (2 * r + 1) ** 3
-        sel, fdec = _mask(n_fine, device), _mask(n_fine, device)
-        _check(L.foho_vol_select(_p(active), _p(dec), r, _p(sel), _p(fdec), st), "foho_vol_select")
-        del mixed, active
-        idx, vals = run(sel, 2 * r)
-        fine = torch.empty(n_fine, dtype=torch.float32, device=device)
-        _check(L.foho_vol_fill(_p(field), r, _p(fine), st), "foho_vol_fill")
-        _check(L.foho_vol_scatter(_p(idx), _p(vals), idx.numel(), _p(fine), st), "foho_vol_scatter")
-        field, dec, r = fine, fdec, 2 * r
-        stats["levels"].append(r)
-        stats["decoded_per_level"].append(int(idx.numel()))
-    # closure at the final level
+        cells, n_fine = r ** 3, (2 * r + 1) ** 3
+        sels, fdec = {}, []
+        for b in imgs:
+            mixed, active = _mask(cells, device), _mask(cells, device)
+            _check(L.foho_vol_mark(_p(field[b]), r, band, _p(mixed), _p(active), st), "foho_vol_mark")
+            sels[b], fd = _mask(n_fine, device), _mask(n_fine, device)
+            _check(L.foho_vol_select(_p(active), _p(dec[b]), r, _p(sels[b]), _p(fd), st), "foho_vol_select")
+            fdec.append(fd)
+            del mixed, active
+        got = emit(sels, 2 * r)
+        for b in imgs:
+            idx, xyz = got[b]
+            vals = _decoded(decodes[b], xyz, idx.numel())
+            fine = torch.empty(n_fine, dtype=torch.float32, device=device)
+            _check(L.foho_vol_fill(_p(field[b]), r, _p(fine), st), "foho_vol_fill")
+            _check(L.foho_vol_scatter(_p(idx), _p(vals), idx.numel(), _p(fine), st), "foho_vol_scatter")
+            field[b] = fine
+            stats[b]["levels"].append(2 * r)
+            stats[b]["decoded_per_level"].append(int(idx.numel()))
+        dec, r = fdec, 2 * r
+    # closure at the final level, for the images that have not settled yet
     cubes = res ** 3
-    bad, near, sel = _mask(cubes, device), _mask(cubes, device), _mask((res + 1) ** 3, device)
-    rounds, closure, fallback = 0, [], False
-    while True:
-        _check(L.foho_vol_close(_p(field), _p(dec), res, 0, _p(bad), _p(near), _p(sel), st), "foho_vol_close")
-        idx, xyz = emit(sel, res)
-        if idx.numel() == 0:
-            break
-        fallback = rounds == max_rounds
-        if fallback:                       # not settled: this round's points and every other point still undecoded
-            _check(L.foho_vol_close(_p(field), _p(dec), res, CLOSE_ALL, None, None, _p(sel), st), "foho_vol_close")
-            idx2, xyz2 = emit(sel, res)
-            idx, order = torch.sort(torch.cat([idx, idx2]))           # one ascending list, like every other decode's
-            xyz = torch.cat([xyz, xyz2])[order]
-        vals = decode(xyz).reshape(-1).to(torch.float32).contiguous()
-        if vals.numel() != idx.numel():
-            raise FohoError(f"hierarchical decode: the decoder returned {vals.numel()} values for {idx.numel()} points")
-        _check(L.foho_vol_scatter(_p(idx), _p(vals), idx.numel(), _p(field), st), "foho_vol_scatter")
-        closure.append(int(idx.numel()))
-        if fallback:
-            break
-        rounds += 1
-    total = sum(stats["decoded_per_level"]) + sum(closure)
-    stats.update(closure_rounds=rounds, closure_decoded=closure, decoded=total, decoded_fraction=total / (res + 1) ** 3,
-                 fallback=fallback, band=band, max_rounds=max_rounds)
-    return field, stats
+    bad, near, sel = _mask(cubes, device), _mask(cubes, device), {b: _mask((res + 1) ** 3, device) for b in imgs}
+    rounds, closure, fallback = [0] * B, [[] for _ in imgs], [False] * B
+    open_ = list(imgs)
+    while open_:
+        for b in open_:
+            _check(L.foho_vol_close(_p(field[b]), _p(dec[b]), res, 0, _p(bad), _p(near), _p(sel[b]), st), "foho_vol_close")
+        got = emit({b: sel[b] for b in open_}, res)
+        open_ = [b for b in open_ if got[b][0].numel()]
+        falls = [b for b in open_ if rounds[b] == max_rounds]
+        for b in falls:                    # not settled: this round's points and every other point still undecoded
+            fallback[b] = True
+            _check(L.foho_vol_close(_p(field[b]), _p(dec[b]), res, CLOSE_ALL, None, None, _p(sel[b]), st), "foho_vol_close")
+        rest = emit({b: sel[b] for b in falls}, res)
+        for b in open_:
+            idx, xyz = got[b]
+            if b in rest:
+                idx2, xyz2 = rest[b]
+                idx, order = torch.sort(torch.cat([idx, idx2]))           # one ascending list, like every other decode's
+                xyz = torch.cat([xyz, xyz2])[order]
+            vals = _decoded(decodes[b], xyz, idx.numel())
+            _check(L.foho_vol_scatter(_p(idx), _p(vals), idx.numel(), _p(field[b]), st), "foho_vol_scatter")
+            closure[b].append(int(idx.numel()))
+            if not fallback[b]:
+                rounds[b] += 1
+        open_ = [b for b in open_ if not fallback[b]]
+    for b in imgs:
+        total = sum(stats[b]["decoded_per_level"]) + sum(closure[b])
+        stats[b].update(closure_rounds=rounds[b], closure_decoded=closure[b], decoded=total, decoded_fraction=total / (res + 1) ** 3,
+                        fallback=fallback[b], band=band, max_rounds=max_rounds)
+    return field, stats, emit.reads
