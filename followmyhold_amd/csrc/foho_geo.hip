@@ -404,350 +404,7 @@ __device__ __forceinline__ unsigned lds_addr(const void* p) {
 }
 #define GEO_DSR(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
 
-template <int EP>
-__global__ __launch_bounds__(256, 2) void k_geo_gemm(const h16* __restrict__ A, int lda, const h16* __restrict__ Wt, int ldw,
-                                                     const float* __restrict__ bias, const h16* __restrict__ R, int ldr,
-                                                     h16* __restrict__ C, int ldc, int M, int N, int K, float scale, h16* __restrict__ C2,
-                                                     int ldc2, const int* __restrict__ Mdev, EpiAux aux = EpiAux{}) {
-    __shared__ uint4 lds[2][2][GM * GK * 2 / 16];  // [buffer][A | W][128 rows x 8 chunks] = 64 KB
-    if (Mdev) M = min(M, *Mdev);   // device-resident row count (foho_geo_decode_bwd_rows): tiles beyond it leave at once
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, hi = lane >> 5, l31 = lane & 31;
-    // XCD-aware tile order: the blocks of one XCD (L mod 8) sweep N inside one row panel of A, eight panels (one per XCD) at a time
-    const int ntn = N / GN, ntm = (M + GM - 1) / GM;
-    const int L = blockIdx.x, xcd = L & 7, j = L >> 3;
-    const int mp = (j / ntn) * 8 + xcd, nt = j % ntn;
-    if (mp >= ntm) return;
-    const int m0 = mp * GM, n0 = nt * GN;
-    const int wr = w >> 1, wc = w & 1;  // this wave's 64 x 64 part of the tile
-
-    // Staging by LDS-DMA (global_load_lds_dwordx4: 64 lanes x 16 B = 8 rows of a tile per instruction, destination lane-linear,
-    // so the XOR swizzle sits on the SOURCE address): no VGPR -> LDS store pass -- register staging had this kernel bound by
-    // the LDS (ds_write_b128 costs 13 cycles per wave-instruction: 832 of them + 512 of fragment reads per K-tile and CU
-    // against 1024 cycles of MFMA).  The fragment reads are INLINE ASM: hipcc cannot tell the DMA's destination buffer
-    // from the one being read and waits vmcnt(0) in front of every compiler-visible ds_read, which serialises the
-    // prefetch with the MFMAs (measured: the first version of this kernel); reads it cannot see get no such wait, and
-    // this code counts lgkmcnt itself.  A wave moves pieces w*4 .. w*4+3 of both operands per K-tile.
-    const int srow = lane >> 3, sslot = lane & 7;
-    const h16* asrc[4];
-    const h16* wsrc[4];
-#pragma unroll
-    for (int p = 0; p < 4; p++) {
-        const int row = (w * 4 + p) * 8 + srow;
-        const int c = sslot ^ swz(row);
-        asrc[p] = A + (size_t)min(m0 + row, M - 1) * lda + c * 8;
-        wsrc[p] = Wt + (size_t)(n0 + row) * ldw + c * 8;
-    }
-
-    f32x16 acc[2][2];  // [n tile][m tile]: D rows = n, D columns = m (the lane holds 4 consecutive n for one m)
-#pragma unroll
-    for (int a = 0; a < 2; a++)
-#pragma unroll
-        for (int b = 0; b < 2; b++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) acc[a][b][r] = 0.0f;
-
-    // fragment byte addresses inside buffer 0: row r, chunk c -> r * 128 + (c ^ swz(r)) * 16; the second tile of a wave
-    // (rows + 32, same swizzle) is an immediate offset of 4096, the W operand one of 16384
-    const int ra = wr * 64 + l31, rw = wc * 64 + l31;
-    const unsigned base = lds_addr(&lds[0][0][0]);
-    unsigned aa[4], aw[4];
-#pragma unroll
-    for (int kk = 0; kk < 4; kk++) {
-        aa[kk] = base + ra * 128 + (((2 * kk + hi) ^ swz(ra)) << 4);
-        aw[kk] = base + rw * 128 + (((2 * kk + hi) ^ swz(rw)) << 4);
-    }
-
-    const int nk = K / GK;
-#pragma unroll
-    for (int p = 0; p < 4; p++) {
-        glds16(asrc[p], &lds[0][0][(w * 4 + p) * 64]);
-        glds16(wsrc[p], &lds[0][1][(w * 4 + p) * 64]);
-    }
-    for (int t = 0; t < nk; t++) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();  // tile t has landed for every wave, and everybody is done reading the other buffer
-        if (t + 1 < nk) {
-            const int nb = (t + 1) & 1, k0 = (t + 1) * GK;
-#pragma unroll
-            for (int p = 0; p < 4; p++) {
-                glds16(asrc[p] + k0, &lds[nb][0][(w * 4 + p) * 64]);
-                glds16(wsrc[p] + k0, &lds[nb][1][(w * 4 + p) * 64]);
-            }
-        }
-        asm volatile("" ::: "memory");
-        const unsigned bo = (unsigned)(t & 1) << 15;  // 32 KB per buffer
-        half8 fa[2][2], fw[2][2];  // [parity of kk][tile]: the fragments of step kk + 1 are requested before step kk's MFMAs issue
-        {
-            const unsigned pa = aa[0] + bo, pw = aw[0] + bo;
-            GEO_DSR(fa[0][0], pa, 0);
-            GEO_DSR(fa[0][1], pa, 4096);
-            GEO_DSR(fw[0][0], pw, 16384);
-            GEO_DSR(fw[0][1], pw, 16384 + 4096);
-        }
-#pragma unroll
-        for (int kk = 0; kk < 4; kk++) {
-            if (kk < 3) {
-                const unsigned pa = aa[kk + 1] + bo, pw = aw[kk + 1] + bo;
-                GEO_DSR(fa[(kk + 1) & 1][0], pa, 0);
-                GEO_DSR(fa[(kk + 1) & 1][1], pa, 4096);
-                GEO_DSR(fw[(kk + 1) & 1][0], pw, 16384);
-                GEO_DSR(fw[(kk + 1) & 1][1], pw, 16384 + 4096);
-                // LDS returns in order: at most the four reads just issued may still be out
-                asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(fa[kk & 1][0]), "+v"(fa[kk & 1][1]), "+v"(fw[kk & 1][0]), "+v"(fw[kk & 1][1]));
-            } else {
-                asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(fa[kk & 1][0]), "+v"(fa[kk & 1][1]), "+v"(fw[kk & 1][0]), "+v"(fw[kk & 1][1]));
-            }
-#pragma unroll
-            for (int jn = 0; jn < 2; jn++)
-#pragma unroll
-                for (int i = 0; i < 2; i++)
-                    acc[jn][i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fw[kk & 1][jn], fa[kk & 1][i], acc[jn][i], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-    __syncthreads();  // every wave is done with the staging buffers: they become the epilogue's transpose image
-
-    // ---- epilogue (gemm_epilogue64): the staging buffers become the waves' transpose images
-    h16* img = reinterpret_cast<h16*>(&lds[0][0][0]) + w * (64 * CPAD);
-    EpiCols pc;
-    EpiRows pr;
-    epi_cols<EP>(pc, bias, ldr, ldc2, n0 + wc * 64, lane);
-    epi_rows<EP>(pr, R, ldr, M, m0 + wr * 64, n0 + wc * 64, lane);
-    gemm_epilogue64<EP>(acc[0][0], acc[0][1], acc[1][0], acc[1][1], img, pc, pr, R, C, ldc, C2, ldc2, M, scale, m0 + wr * 64, n0 + wc * 64, lane, bias, ldr, aux);
-}
-
-// ------------------------------------------------------------------------------------------------
-// The 128 x 128 x 64 GEMM with a FOUR-deep LDS ring (round 6), for launches that put at most one workgroup on a CU -- the N = 1024
-// products of the ShapeVAE transformer at M = 3072 (192 tiles on 256 CUs: c_proj, fc2 and the three transposed-weight GEMMs of the
-// backward).  k_geo_gemm issues a tile's eight LDS-DMA pieces per wave in one block in front of the tile's matrix instructions; a wave
-// is held ~80 cycles per piece, and with ONE wave per SIMD (one workgroup per CU) nothing else feeds the matrix pipe meanwhile:
-// 0.65 us per K tile against 0.21 us of matrix work (0.93 us inside the transformer chain: 59 us for K = 4096).  A deeper ring ALONE
-// changed nothing (measured: the latency was never the limit).  Here tile t + 3 is issued while tile t is multiplied (4 x 32 KB of
-// LDS) and a wave waits for
-// its OWN oldest tile with a counted s_waitcnt vmcnt(16) (two newer tiles of 8 pieces stay in flight) before the barrier that
-// publishes the tile to the other waves.  Same fragments, same epilogue as k_geo_gemm.
-// ------------------------------------------------------------------------------------------------
-template <int EP>
-__global__ __launch_bounds__(256, 1) void k_geo_gemm_d4(const h16* __restrict__ A, int lda, const h16* __restrict__ Wt, int ldw,
-                                                        const float* __restrict__ bias, const h16* __restrict__ R, int ldr,
-                                                        h16* __restrict__ C, int ldc, int M, int N, int K, float scale, h16* __restrict__ C2,
-                                                        int ldc2, const int* __restrict__ Mdev, EpiAux aux = EpiAux{}) {
-    __shared__ uint4 lds[4][2][GM * GK * 2 / 16];  // [stage][A | W][128 rows x 8 chunks] = 128 KB
-    if (Mdev) M = min(M, *Mdev);
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, hi = lane >> 5, l31 = lane & 31;
-    const int ntn = N / GN, ntm = (M + GM - 1) / GM;
-    const int L = blockIdx.x, xcd = L & 7, j = L >> 3;
-    const int mp = (j / ntn) * 8 + xcd, nt = j % ntn;
-    if (mp >= ntm) return;
-    const int m0 = mp * GM, n0 = nt * GN;
-    const int wr = w >> 1, wc = w & 1;
-    const int srow = lane >> 3, sslot = lane & 7;
-    const h16* asrc[4];
-    const h16* wsrc[4];
-#pragma unroll
-    for (int p = 0; p < 4; p++) {
-        const int row = (w * 4 + p) * 8 + srow;
-        const int c = sslot ^ swz(row);
-        asrc[p] = A + (size_t)min(m0 + row, M - 1) * lda + c * 8;
-        wsrc[p] = Wt + (size_t)(n0 + row) * ldw + c * 8;
-    }
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; a++)
-#pragma unroll
-        for (int b = 0; b < 2; b++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) acc[a][b][r] = 0.0f;
-    const int ra = wr * 64 + l31, rw = wc * 64 + l31;
-    const unsigned base = lds_addr(&lds[0][0][0]);
-    unsigned aa[4], aw[4];
-#pragma unroll
-    for (int kk = 0; kk < 4; kk++) {
-        aa[kk] = base + ra * 128 + (((2 * kk + hi) ^ swz(ra)) << 4);
-        aw[kk] = base + rw * 128 + (((2 * kk + hi) ^ swz(rw)) << 4);
-    }
-    const int nk = K / GK;
-#define D4_ISSUE(t_)                                                        \
-    do {                                                                    \
-        const int sb_ = (t_) & 3, k0_ = (t_) * GK;                          \
-        _Pragma("unroll") for (int p = 0; p < 4; p++) {                     \
-            glds16(asrc[p] + k0_, &lds[sb_][0][(w * 4 + p) * 64]);          \
-            glds16(wsrc[p] + k0_, &lds[sb_][1][(w * 4 + p) * 64]);          \
-        }                                                                   \
-    } while (0)
-    for (int t = 0; t < 3 && t < nk; t++) D4_ISSUE(t);
-    P8_STAMP_DECL;   // (development builds -DP8_STAMPS: per-wave sums of a K tile's segments, foho_geo_stamps.h; empty otherwise)
-    for (int t = 0; t < nk; t++) {
-        // this wave's pieces of tile t have landed when at most the pieces of the newer tiles in flight remain outstanding
-        if (t + 2 < nk) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-        else if (t + 1 < nk) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        P8_STAMP(1);
-        // RAW barrier: __syncthreads() fences with s_waitcnt vmcnt(0) -- an LDS-DMA in flight is a pending LDS write -- and would drain the
-        // ring at every tile (the first build of this kernel did: no faster than two stages).  This wave's own reads of stage (t - 1) & 3
-        // completed with the lgkmcnt(0) of the previous tile's last k step.
-        __builtin_amdgcn_s_barrier();  // tile t has landed for every wave, and everybody is done reading stage (t - 1) & 3 -- where tile t + 3 goes
-        P8_STAMP(2);
-        if (t + 3 < nk) D4_ISSUE(t + 3);   // (in ONE block: two pieces behind each k step's matrix instructions measured 55.6 against 41.8 us at K = 4096)
-        P8_STAMP(3);
-        asm volatile("" ::: "memory");
-        const unsigned bo = (unsigned)(t & 3) << 15;  // 32 KB per stage
-#ifdef D4_FILL_ONLY   // (development build: the ring's fill alone -- no fragment reads, no matrix instructions; results are garbage)
-        continue;
-#endif
-        half8 fa[2][2], fw[2][2];
-        {
-            const unsigned pa = aa[0] + bo, pw = aw[0] + bo;
-            GEO_DSR(fa[0][0], pa, 0);
-            GEO_DSR(fa[0][1], pa, 4096);
-            GEO_DSR(fw[0][0], pw, 16384);
-            GEO_DSR(fw[0][1], pw, 16384 + 4096);
-        }
-#pragma unroll
-        for (int kk = 0; kk < 4; kk++) {
-            if (kk < 3) {
-                const unsigned pa = aa[kk + 1] + bo, pw = aw[kk + 1] + bo;
-                GEO_DSR(fa[(kk + 1) & 1][0], pa, 0);
-                GEO_DSR(fa[(kk + 1) & 1][1], pa, 4096);
-                GEO_DSR(fw[(kk + 1) & 1][0], pw, 16384);
-                GEO_DSR(fw[(kk + 1) & 1][1], pw, 16384 + 4096);
-                asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(fa[kk & 1][0]), "+v"(fa[kk & 1][1]), "+v"(fw[kk & 1][0]), "+v"(fw[kk & 1][1]));
-                if (kk == 0) P8_STAMP(4);
-            } else {
-                asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(fa[kk & 1][0]), "+v"(fa[kk & 1][1]), "+v"(fw[kk & 1][0]), "+v"(fw[kk & 1][1]));
-            }
-#pragma unroll
-            for (int jn = 0; jn < 2; jn++)
-#pragma unroll
-                for (int i = 0; i < 2; i++)
-                    acc[jn][i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fw[kk & 1][jn], fa[kk & 1][i], acc[jn][i], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            if (kk == 1) P8_STAMP(5);
-        }
-        P8_STAMP(6);
-        P8_ACC();
-    }
-    P8_STAMP_DUMP(w, nk);
-#undef D4_ISSUE
-    __syncthreads();  // every wave is done with the ring: it becomes the epilogue's transpose image
-    h16* img = reinterpret_cast<h16*>(&lds[0][0][0]) + w * (64 * CPAD);
-    EpiCols pc;
-    EpiRows pr;
-    epi_cols<EP>(pc, bias, ldr, ldc2, n0 + wc * 64, lane);
-    epi_rows<EP>(pr, R, ldr, M, m0 + wr * 64, n0 + wc * 64, lane);
-    gemm_epilogue64<EP>(acc[0][0], acc[0][1], acc[1][0], acc[1][1], img, pc, pr, R, C, ldc, C2, ldc2, M, scale, m0 + wr * 64, n0 + wc * 64, lane, bias, ldr, aux);
-}
-
-// ------------------------------------------------------------------------------------------------
-// k_geo_gemm_d4 with the FILL and the MATRIX work on different waves (round 6): a CU fills its LDS at ~86 GB/s (382 ns per 32 KB K tile)
-// and a wave that issues LDS-DMA issues nothing else, so at one wave per SIMD fill time and matrix time add (0.68 us per K tile,
-// NOTEBOOK round 6).  Eight waves: waves 4-7 only fill the four-deep ring, waves 0-3 only read fragments and multiply; one raw barrier
-// per K tile hands tile t over and frees stage (t - 1) & 3.  The consumers run the epilogue.
-// ------------------------------------------------------------------------------------------------
-template <int EP>
-__global__ __launch_bounds__(512, 1) void k_geo_gemm_pc(const h16* __restrict__ A, int lda, const h16* __restrict__ Wt, int ldw,
-                                                        const float* __restrict__ bias, const h16* __restrict__ R, int ldr,
-                                                        h16* __restrict__ C, int ldc, int M, int N, int K, float scale, h16* __restrict__ C2,
-                                                        int ldc2, const int* __restrict__ Mdev, EpiAux aux = EpiAux{}) {
-    __shared__ uint4 lds[4][2][GM * GK * 2 / 16];  // [stage][A | W][128 rows x 8 chunks] = 128 KB
-    if (Mdev) M = min(M, *Mdev);
-    const int tid = threadIdx.x, lane = tid & 63, hi = lane >> 5, l31 = lane & 31;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const bool producer = wv >= 4;   // waves 4-7 only FILL the ring (each the eight pieces wave wv - 4 would), waves 0-3 only multiply
-    const int w = wv & 3;
-    const int ntn = N / GN, ntm = (M + GM - 1) / GM;
-    const int L = blockIdx.x, xcd = L & 7, j = L >> 3;
-    const int mp = (j / ntn) * 8 + xcd, nt = j % ntn;
-    if (mp >= ntm) return;
-    const int m0 = mp * GM, n0 = nt * GN;
-    const int wr = w >> 1, wc = w & 1;
-    const int srow = lane >> 3, sslot = lane & 7;
-    const h16* asrc[4];
-    const h16* wsrc[4];
-#pragma unroll
-    for (int p = 0; p < 4; p++) {
-        const int row = (w * 4 + p) * 8 + srow;
-        const int c = sslot ^ swz(row);
-        asrc[p] = A + (size_t)min(m0 + row, M - 1) * lda + c * 8;
-        wsrc[p] = Wt + (size_t)(n0 + row) * ldw + c * 8;
-    }
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; a++)
-#pragma unroll
-        for (int b = 0; b < 2; b++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) acc[a][b][r] = 0.0f;
-    const int ra = wr * 64 + l31, rw = wc * 64 + l31;
-    const unsigned base = lds_addr(&lds[0][0][0]);
-    unsigned aa[4], aw[4];
-#pragma unroll
-    for (int kk = 0; kk < 4; kk++) {
-        aa[kk] = base + ra * 128 + (((2 * kk + hi) ^ swz(ra)) << 4);
-        aw[kk] = base + rw * 128 + (((2 * kk + hi) ^ swz(rw)) << 4);
-    }
-    const int nk = K / GK;
-#define D4_ISSUE(t_)                                                        \
-    do {                                                                    \
-        const int sb_ = (t_) & 3, k0_ = (t_) * GK;                          \
-        _Pragma("unroll") for (int p = 0; p < 4; p++) {                     \
-            glds16(asrc[p] + k0_, &lds[sb_][0][(w * 4 + p) * 64]);          \
-            glds16(wsrc[p] + k0_, &lds[sb_][1][(w * 4 + p) * 64]);          \
-        }                                                                   \
-    } while (0)
-    if (producer) {
-        for (int t = 0; t < 3 && t < nk; t++) D4_ISSUE(t);
-        for (int t = 0; t < nk; t++) {
-            if (t + 2 < nk) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-            else if (t + 1 < nk) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();   // tile t has landed (every producer waited for its pieces); the consumers are done with tile t - 1
-            if (t + 3 < nk) D4_ISSUE(t + 3);
-        }
-        __syncthreads();
-        return;
-    }
-    for (int t = 0; t < nk; t++) {
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        const unsigned bo = (unsigned)(t & 3) << 15;  // 32 KB per stage
-        half8 fa[2][2], fw[2][2];
-        {
-            const unsigned pa = aa[0] + bo, pw = aw[0] + bo;
-            GEO_DSR(fa[0][0], pa, 0);
-            GEO_DSR(fa[0][1], pa, 4096);
-            GEO_DSR(fw[0][0], pw, 16384);
-            GEO_DSR(fw[0][1], pw, 16384 + 4096);
-        }
-#pragma unroll
-        for (int kk = 0; kk < 4; kk++) {
-            if (kk < 3) {
-                const unsigned pa = aa[kk + 1] + bo, pw = aw[kk + 1] + bo;
-                GEO_DSR(fa[(kk + 1) & 1][0], pa, 0);
-                GEO_DSR(fa[(kk + 1) & 1][1], pa, 4096);
-                GEO_DSR(fw[(kk + 1) & 1][0], pw, 16384);
-                GEO_DSR(fw[(kk + 1) & 1][1], pw, 16384 + 4096);
-                asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(fa[kk & 1][0]), "+v"(fa[kk & 1][1]), "+v"(fw[kk & 1][0]), "+v"(fw[kk & 1][1]));
-            } else {
-                asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(fa[kk & 1][0]), "+v"(fa[kk & 1][1]), "+v"(fw[kk & 1][0]), "+v"(fw[kk & 1][1]));
-            }
-#pragma unroll
-            for (int jn = 0; jn < 2; jn++)
-#pragma unroll
-                for (int i = 0; i < 2; i++)
-                    acc[jn][i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fw[kk & 1][jn], fa[kk & 1][i], acc[jn][i], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-#undef D4_ISSUE
-    __syncthreads();  // every wave is done with the ring: it becomes the epilogue's transpose image
-    h16* img = reinterpret_cast<h16*>(&lds[0][0][0]) + w * (64 * CPAD);
-    EpiCols pc;
-    EpiRows pr;
-    epi_cols<EP>(pc, bias, ldr, ldc2, n0 + wc * 64, lane);
-    epi_rows<EP>(pr, R, ldr, M, m0 + wr * 64, n0 + wc * 64, lane);
-    gemm_epilogue64<EP>(acc[0][0], acc[0][1], acc[1][0], acc[1][1], img, pc, pr, R, C, ldc, C2, ldc2, M, scale, m0 + wr * 64, n0 + wc * 64, lane, bias, ldr, aux);
-}
+#include "geo_gemm128.inc"   // k_geo_gemm, k_geo_gemm_d4, k_geo_gemm_pc: the 128 x 128 x 64 tile (Tile128) and its three ring schedules
 
 // ------------------------------------------------------------------------------------------------
 // The same GEMM on 256 x 256 x 64 tiles, 8 waves x (128 x 64): per K-tile a wave still issues 8 LDS-DMA pieces, but 64 MFMAs
@@ -2544,34 +2201,39 @@ static int check_weights(const foho_geo_weights* w) {
     return FOHO_OK;
 }
 
+// Bump allocator of the workspace layouts: byte offsets, every block rounded up to 256 bytes; `off` ends as the total.
+struct Carve {
+    size_t off = 0;
+    size_t bytes(size_t n) {
+        const size_t o = off;
+        off += (n + 255) & ~(size_t)255;
+        return o;
+    }
+};
+
 struct Layout {
     size_t kv, vt, e, a, b, c, h, w1f, fold1, fold2, stats, rowstat, total;
 };
 static Layout layout(const foho_geo_weights* w, int chunk) {
     Layout l{};
-    size_t off = 0;
-    auto take = [&](size_t halfs) {
-        const size_t o = off;
-        off += (halfs * 2 + 255) & ~(size_t)255;
-        return o;
-    };
-    const size_t W = w->width, Lr = w->n_latents, rows = std::max<size_t>(chunk, Lr);  // the prepare step normalises the latents in buffer A
-    l.kv = take(Lr * 2 * W);
-    l.vt = take(W * Lr);
+    Carve cv;
+    const size_t W = w->width, F = w->hidden, C = chunk, Lr = w->n_latents, rows = std::max<size_t>(chunk, Lr);  // the prepare step normalises the latents in buffer A
+    l.kv = cv.bytes(Lr * 2 * W * 2);
+    l.vt = cv.bytes(W * Lr * 2);
     // LayerNorm folded into the forward GEMMs (chain_latent_side): fc1's weights with ln_2's gain and the folded vectors -- like kv / vt
     // written by the prepare step, at offsets that do not depend on the chunk
-    l.w1f = take((size_t)w->hidden * W);
-    l.fold1 = take((size_t)w->hidden * 4);        // 2 hidden floats
-    l.fold2 = take((size_t)W * 4 + 8);            // 2 W + 2 floats
-    l.e = take((size_t)chunk * 64);
-    l.a = take(rows * W);
-    l.b = take((size_t)chunk * W);
-    l.c = take((size_t)chunk * W);
-    l.h = take((size_t)chunk * w->hidden);
+    l.w1f = cv.bytes(F * W * 2);
+    l.fold1 = cv.bytes(2 * F * 4);               // 2 hidden floats
+    l.fold2 = cv.bytes((2 * W + 4) * 4);         // 2 W + 2 floats, in room for 2 W + 4
+    l.e = cv.bytes(C * 64 * 2);
+    l.a = cv.bytes(rows * W * 2);
+    l.b = cv.bytes(C * W * 2);
+    l.c = cv.bytes(C * W * 2);
+    l.h = cv.bytes(C * F * 2);
     // ... the per-row statistics of the folded LayerNorms (16 parts of 4 floats at width 1024) and (rstd, rstd mean) per row
-    l.stats = take((size_t)chunk * (W / 64) * 8); // chunk x parts x 4 floats
-    l.rowstat = take((size_t)chunk * 4);          // chunk x 2 floats
-    l.total = off;
+    l.stats = cv.bytes(C * (W / 64) * 4 * 4);    // chunk x parts x 4 floats
+    l.rowstat = cv.bytes(C * 2 * 4);             // chunk x 2 floats
+    l.total = cv.off;
     return l;
 }
 struct Fold {   // device pointers of the folded operands in a prepared workspace (w1f == nullptr: chain with LayerNorm kernels)
@@ -2594,6 +2256,27 @@ static int fold_weights(const foho_geo_weights* w, const Layout& l, char* base, 
     return launch_ok("k_geo_fold") ? FOHO_OK : FOHO_ERR_LAUNCH;
 }
 
+
+// A prepared workspace as an entry point sees it: its layout and the K | V projection and V^T of the latent tokens in it.
+struct Ws {
+    Layout l;
+    char* base;
+    h16 *kv, *vt;
+};
+static Ws ws_of(const foho_geo_weights* w, int chunk, void* ws) {
+    Ws o{layout(w, chunk), (char*)ws, nullptr, nullptr};
+    o.kv = (h16*)(o.base + o.l.kv), o.vt = (h16*)(o.base + o.l.vt);
+    return o;
+}
+// The preamble of an entry point `who`: the weights, its own arguments (args_ok; it covers ws != NULL and chunk_rows > 0), the workspace's size.
+static int open_ws(const char* who, const foho_geo_weights* w, bool args_ok, int chunk, void* ws, size_t ws_bytes, Ws& o) {
+    if (int rc = check_weights(w)) return rc;
+    if (!args_ok) return fail(FOHO_ERR_BAD_ARG, std::string(who) + ": null argument");
+    o = ws_of(w, chunk, ws);
+    if (ws_bytes < o.l.total) return fail(FOHO_ERR_WORKSPACE, std::string(who) + ": workspace too small");
+    return FOHO_OK;
+}
+
 }  // namespace geo
 
 using namespace geo;
@@ -2608,13 +2291,12 @@ extern "C" size_t foho_geo_workspace_bytes(const foho_geo_weights* w, int32_t ch
 }
 
 extern "C" int foho_geo_prepare(const foho_geo_weights* w, const void* latents, int32_t chunk_rows, void* ws, size_t ws_bytes, void* stream_) {
-    if (int rc = check_weights(w)) return rc;
-    if (!latents || !ws || chunk_rows <= 0) return fail(FOHO_ERR_BAD_ARG, "foho_geo_prepare: null argument");
-    const Layout l = layout(w, chunk_rows);
-    if (ws_bytes < l.total) return fail(FOHO_ERR_WORKSPACE, "foho_geo_prepare: workspace too small");
+    Ws o;
+    if (int rc = open_ws("foho_geo_prepare", w, latents && ws && chunk_rows > 0, chunk_rows, ws, ws_bytes, o)) return rc;
     hipStream_t s = (hipStream_t)stream_;
-    char* base = (char*)ws;
-    h16 *kv = (h16*)(base + l.kv), *vt = (h16*)(base + l.vt), *ln = (h16*)(base + l.a);
+    const Layout& l = o.l;
+    char* base = o.base;
+    h16 *kv = o.kv, *vt = o.vt, *ln = (h16*)(base + l.a);
     const int W = w->width, Lr = w->n_latents;
     hipLaunchKernelGGL(k_geo_ln<0>, dim3((Lr + 3) / 4), dim3(256), 0, s, (const h16*)latents, W, w->ln_kv_g, w->ln_kv_b, ln, W, Lr, W, eps_of(w, w->ln_kv_eps),
                        (const float*)nullptr, 0.0f, (const float*)nullptr, 0.0f, 0.0f, 0.0f, (float*)nullptr, (const int*)nullptr);
@@ -2695,13 +2377,12 @@ static int chain_logits(const foho_geo_weights* w, const float* q, int M, const 
 
 extern "C" int foho_geo_decode_fwd(const foho_geo_weights* w, const float* queries, int64_t n_queries, float* logits, int32_t chunk_rows,
                                    void* ws, size_t ws_bytes, void* stream_) {
-    if (int rc = check_weights(w)) return rc;
-    if (!queries || !logits || !ws || chunk_rows <= 0 || n_queries < 0) return fail(FOHO_ERR_BAD_ARG, "foho_geo_decode_fwd: null argument");
-    const Layout l = layout(w, chunk_rows);
-    if (ws_bytes < l.total) return fail(FOHO_ERR_WORKSPACE, "foho_geo_decode_fwd: workspace too small");
+    Ws o;
+    if (int rc = open_ws("foho_geo_decode_fwd", w, queries && logits && ws && chunk_rows > 0 && n_queries >= 0, chunk_rows, ws, ws_bytes, o)) return rc;
     hipStream_t s = (hipStream_t)stream_;
-    char* base = (char*)ws;
-    const h16 *kv = (const h16*)(base + l.kv), *vt = (const h16*)(base + l.vt);
+    const Layout& l = o.l;
+    char* base = o.base;
+    const h16 *kv = o.kv, *vt = o.vt;
     h16 *E = (h16*)(base + l.e), *bA = (h16*)(base + l.a), *bB = (h16*)(base + l.b), *bC = (h16*)(base + l.c), *bH = (h16*)(base + l.h);
     const Fold fold = fold_of(w, l, base);
     for (int64_t r0 = 0; r0 < n_queries; r0 += chunk_rows) {
@@ -2734,14 +2415,13 @@ extern "C" size_t foho_geo_query_cache_bytes(const foho_geo_weights* w, int64_t 
 
 extern "C" int foho_geo_prepare_queries(const foho_geo_weights* w, const float* queries, int64_t n_queries, int32_t chunk_rows, void* ws, size_t ws_bytes,
                                         void* cache, size_t cache_bytes, void* stream_) {
-    if (int rc = check_weights(w)) return rc;
-    if (!queries || !ws || !cache || chunk_rows <= 0 || n_queries < 0) return fail(FOHO_ERR_BAD_ARG, "foho_geo_prepare_queries: null argument");
-    const Layout l = layout(w, chunk_rows);
+    Ws o;
+    if (int rc = open_ws("foho_geo_prepare_queries", w, queries && ws && cache && chunk_rows > 0 && n_queries >= 0, chunk_rows, ws, ws_bytes, o)) return rc;
+    const Layout& l = o.l;
     const CacheLayout c = cache_layout(w, n_queries);
-    if (ws_bytes < l.total) return fail(FOHO_ERR_WORKSPACE, "foho_geo_prepare_queries: workspace too small");
     if (cache_bytes < c.total) return fail(FOHO_ERR_WORKSPACE, "foho_geo_prepare_queries: cache too small (foho_geo_query_cache_bytes)");
     hipStream_t s = (hipStream_t)stream_;
-    char* base = (char*)ws;
+    char* base = o.base;
     h16 *E = (h16*)(base + l.e), *bB = (h16*)(base + l.b);
     h16 *X0 = (h16*)((char*)cache + c.x0), *Qs = (h16*)((char*)cache + c.qs);
     const size_t W = w->width;
@@ -2754,15 +2434,14 @@ extern "C" int foho_geo_prepare_queries(const foho_geo_weights* w, const float* 
 
 extern "C" int foho_geo_decode_fwd_cached(const foho_geo_weights* w, const float* queries, int64_t n_queries, const void* cache, size_t cache_bytes,
                                           float* logits, int32_t chunk_rows, void* ws, size_t ws_bytes, void* stream_) {
-    if (int rc = check_weights(w)) return rc;
-    if (!queries || !cache || !logits || !ws || chunk_rows <= 0 || n_queries < 0) return fail(FOHO_ERR_BAD_ARG, "foho_geo_decode_fwd_cached: null argument");
-    const Layout l = layout(w, chunk_rows);
+    Ws o;
+    if (int rc = open_ws("foho_geo_decode_fwd_cached", w, queries && cache && logits && ws && chunk_rows > 0 && n_queries >= 0, chunk_rows, ws, ws_bytes, o)) return rc;
+    const Layout& l = o.l;
     const CacheLayout c = cache_layout(w, n_queries);
-    if (ws_bytes < l.total) return fail(FOHO_ERR_WORKSPACE, "foho_geo_decode_fwd_cached: workspace too small");
     if (cache_bytes < c.total) return fail(FOHO_ERR_WORKSPACE, "foho_geo_decode_fwd_cached: cache too small");
     hipStream_t s = (hipStream_t)stream_;
-    char* base = (char*)ws;
-    const h16 *kv = (const h16*)(base + l.kv), *vt = (const h16*)(base + l.vt);
+    char* base = o.base;
+    const h16 *kv = o.kv, *vt = o.vt;
     h16 *bA = (h16*)(base + l.a), *bB = (h16*)(base + l.b), *bC = (h16*)(base + l.c), *bH = (h16*)(base + l.h);
     const Fold fold = fold_of(w, l, base);
     const h16 *X0 = (const h16*)((const char*)cache + c.x0), *Qs = (const h16*)((const char*)cache + c.qs);
@@ -2796,31 +2475,26 @@ static int bwd_splits(const foho_geo_weights* w, int chunk) {
 }
 static BwdLayout bwd_layout(const foho_geo_weights* w, int chunk) {
     BwdLayout l{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return o;
-    };
+    Carve cv;
     const size_t W = w->width, F = w->hidden, C = chunk;
     l.ldt = (chunk + 63) & ~63;
-    l.e = take(C * 64 * 2);
-    l.x0 = take(C * W * 2);
-    l.xn = take(C * W * 2);
-    l.qs = take(C * W * 2);
-    l.qst = take(W * (size_t)l.ldt * 2);
-    l.at = take(C * W * 2);
-    l.x1 = take(C * W * 2);
-    l.z = take(C * F * 2);
-    l.h = take(C * F * 2);
-    l.x2 = take(C * W * 2);
-    l.dx2 = take(C * W * 2);
-    l.dat = take(W * (size_t)l.ldt * 2);
-    l.lse = take((size_t)l.ldt * w->heads * 4);    // rows up to the next multiple of 64: the padding of the last query tile
-    l.delta = take((size_t)l.ldt * w->heads * 4);
+    l.e = cv.bytes(C * 64 * 2);
+    l.x0 = cv.bytes(C * W * 2);
+    l.xn = cv.bytes(C * W * 2);
+    l.qs = cv.bytes(C * W * 2);
+    l.qst = cv.bytes(W * (size_t)l.ldt * 2);
+    l.at = cv.bytes(C * W * 2);
+    l.x1 = cv.bytes(C * W * 2);
+    l.z = cv.bytes(C * F * 2);
+    l.h = cv.bytes(C * F * 2);
+    l.x2 = cv.bytes(C * W * 2);
+    l.dx2 = cv.bytes(C * W * 2);
+    l.dat = cv.bytes(W * (size_t)l.ldt * 2);
+    l.lse = cv.bytes((size_t)l.ldt * w->heads * 4);    // rows up to the next multiple of 64: the padding of the last query tile
+    l.delta = cv.bytes((size_t)l.ldt * w->heads * 4);
     l.splits = bwd_splits(w, chunk);
-    l.part = take((size_t)l.splits * w->n_latents * 2 * W * 4);
-    l.total = off;
+    l.part = cv.bytes((size_t)l.splits * w->n_latents * 2 * W * 4);
+    l.total = cv.off;
     return l;
 }
 
@@ -2830,18 +2504,15 @@ extern "C" size_t foho_geo_bwd_workspace_bytes(const foho_geo_weights* w, int32_
 }
 
 extern "C" int foho_geo_set_kv(const foho_geo_weights* w, const void* kv_in, int32_t chunk_rows, void* ws, size_t ws_bytes, void* stream_) {
-    if (int rc = check_weights(w)) return rc;
-    if (!kv_in || !ws || chunk_rows <= 0) return fail(FOHO_ERR_BAD_ARG, "foho_geo_set_kv: null argument");
-    const Layout l = layout(w, chunk_rows);
-    if (ws_bytes < l.total) return fail(FOHO_ERR_WORKSPACE, "foho_geo_set_kv: workspace too small");
+    Ws o;
+    if (int rc = open_ws("foho_geo_set_kv", w, kv_in && ws && chunk_rows > 0, chunk_rows, ws, ws_bytes, o)) return rc;
     hipStream_t s = (hipStream_t)stream_;
-    char* base = (char*)ws;
-    h16 *kv = (h16*)(base + l.kv), *vt = (h16*)(base + l.vt);
+    h16 *kv = o.kv, *vt = o.vt;
     const int W = w->width, Lr = w->n_latents;
     if (hipMemcpyAsync(kv, kv_in, (size_t)Lr * 2 * W * 2, hipMemcpyDeviceToDevice, s) != hipSuccess) return fail(FOHO_ERR_LAUNCH, "foho_geo_set_kv: copy failed");
     hipLaunchKernelGGL(k_geo_pack_vt, dim3((W + 255) / 256, Lr / 16), dim3(256), 0, s, kv, 2 * W, W, Lr, vt);
     if (!launch_ok("k_geo_pack_vt")) return FOHO_ERR_LAUNCH;
-    return fold_weights(w, l, base, s);
+    return fold_weights(w, o.l, o.base, s);
 }
 
 // What the backward of one row block needs from its forward: per block in the `save` buffer (kept mode) or in the backward
@@ -2851,21 +2522,16 @@ struct SavedLayout {
 };
 static SavedLayout saved_layout(const foho_geo_weights* w, int chunk) {
     SavedLayout l{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return o;
-    };
+    Carve cv;
     const size_t W = w->width, F = w->hidden, C = chunk, ldt = (chunk + 63) & ~63;
-    l.qs = take(C * W * 2);
-    l.qst = take(W * ldt * 2);
-    l.at = take(C * W * 2);
-    l.x1 = take(C * W * 2);
-    l.z = take(C * F * 2);
-    l.x2 = take(C * W * 2);
-    l.lse = take(ldt * (size_t)w->heads * 4);
-    l.total = off;
+    l.qs = cv.bytes(C * W * 2);
+    l.qst = cv.bytes(W * ldt * 2);
+    l.at = cv.bytes(C * W * 2);
+    l.x1 = cv.bytes(C * W * 2);
+    l.z = cv.bytes(C * F * 2);
+    l.x2 = cv.bytes(C * W * 2);
+    l.lse = cv.bytes(ldt * (size_t)w->heads * 4);
+    l.total = cv.off;
     return l;
 }
 struct ChunkPtrs {
@@ -2934,13 +2600,13 @@ static int bwd_args(const char* who, const foho_geo_weights* w, const void* a, c
 extern "C" int foho_geo_decode_fwd_keep(const foho_geo_weights* w, const float* queries, int64_t n_queries, float* logits, int32_t chunk_rows, void* ws,
                                         size_t ws_bytes, void* bws, size_t bws_bytes, void* saved, size_t saved_bytes, void* stream_) {
     if (int rc = bwd_args("foho_geo_decode_fwd_keep", w, queries, logits, ws, bws, chunk_rows, n_queries, false)) return rc;
-    const Layout l = layout(w, chunk_rows);
+    const Ws o = ws_of(w, chunk_rows, ws);
     const BwdLayout b = bwd_layout(w, chunk_rows);
     const SavedLayout sl = saved_layout(w, chunk_rows);
-    if (ws_bytes < l.total || bws_bytes < b.total) return fail(FOHO_ERR_WORKSPACE, "foho_geo_decode_fwd_keep: workspace too small");
+    if (ws_bytes < o.l.total || bws_bytes < b.total) return fail(FOHO_ERR_WORKSPACE, "foho_geo_decode_fwd_keep: workspace too small");
     if (!saved || saved_bytes < foho_geo_saved_bytes(w, chunk_rows, n_queries)) return fail(FOHO_ERR_WORKSPACE, "foho_geo_decode_fwd_keep: buffer for the activations too small");
     hipStream_t s = (hipStream_t)stream_;
-    const h16 *kv = (const h16*)((char*)ws + l.kv), *vt = (const h16*)((char*)ws + l.vt);
+    const h16 *kv = o.kv, *vt = o.vt;
     for (int64_t r0 = 0, c = 0; r0 < n_queries; r0 += chunk_rows, c++) {
         const int M = (int)std::min<int64_t>(chunk_rows, n_queries - r0);
         const ChunkPtrs P = chunk_ptrs(b, (char*)bws, sl, (char*)saved + c * sl.total);
@@ -2957,13 +2623,13 @@ extern "C" int foho_geo_decode_bwd(const foho_geo_weights* w, const float* queri
                                    void* stream_) {
     if (int rc = bwd_args("foho_geo_decode_bwd", w, queries, grad_logits, ws, bws, chunk_rows, n_queries, true)) return rc;
     if (!grad_kv) return fail(FOHO_ERR_BAD_ARG, "foho_geo_decode_bwd: null argument");
-    const Layout l = layout(w, chunk_rows);
+    const Ws o = ws_of(w, chunk_rows, ws);
     const BwdLayout b = bwd_layout(w, chunk_rows);
     const SavedLayout sl = saved_layout(w, chunk_rows);
-    if (ws_bytes < l.total || bws_bytes < b.total) return fail(FOHO_ERR_WORKSPACE, "foho_geo_decode_bwd: workspace too small");
+    if (ws_bytes < o.l.total || bws_bytes < b.total) return fail(FOHO_ERR_WORKSPACE, "foho_geo_decode_bwd: workspace too small");
     if (saved && saved_bytes < foho_geo_saved_bytes(w, chunk_rows, n_queries)) return fail(FOHO_ERR_WORKSPACE, "foho_geo_decode_bwd: buffer of activations too small");
     hipStream_t s = (hipStream_t)stream_;
-    const h16 *kv = (const h16*)((char*)ws + l.kv), *vt = (const h16*)((char*)ws + l.vt);
+    const h16 *kv = o.kv, *vt = o.vt;
     char* base = (char*)bws;
     const int W = w->width, Lr = w->n_latents;
     // columns of the transposed copies beyond a ragged block's rows must be finite (they meet P = 0): clear them once
@@ -2996,20 +2662,15 @@ struct RowsLayout {
 constexpr int ROWS_PER_WG = 2048;
 static RowsLayout rows_layout(int64_t n, int64_t cap, int chunk) {
     RowsLayout l{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return o;
-    };
+    Carve cv;
     l.nscan = (int)((n + ROWS_PER_WG - 1) / ROWS_PER_WG);
     l.nblk = (int)std::max<int64_t>((cap + chunk - 1) / chunk, 1);
-    l.counts = take((size_t)std::max(l.nscan, 1) * 4);
-    l.mblk = take((size_t)(std::max(l.nblk, 1) + 2) * 4);     // [0]: the count, [1]: rows dropped for lack of capacity, [2 + c]: rows of block c
-    l.q = take((size_t)std::max<int64_t>(cap, 1) * 12);
-    l.g = take((size_t)std::max<int64_t>(cap, 1) * 4);
-    l.idx = take((size_t)std::max<int64_t>(cap, 1) * 4);
-    l.total = off;
+    l.counts = cv.bytes((size_t)std::max(l.nscan, 1) * 4);
+    l.mblk = cv.bytes((size_t)(std::max(l.nblk, 1) + 2) * 4);     // [0]: the count, [1]: rows dropped for lack of capacity, [2 + c]: rows of block c
+    l.q = cv.bytes((size_t)std::max<int64_t>(cap, 1) * 12);
+    l.g = cv.bytes((size_t)std::max<int64_t>(cap, 1) * 4);
+    l.idx = cv.bytes((size_t)std::max<int64_t>(cap, 1) * 4);
+    l.total = cv.off;
     return l;
 }
 
@@ -3026,13 +2687,13 @@ extern "C" int foho_geo_decode_bwd_rows(const foho_geo_weights* w, const float* 
     if (!grad_kv || !rows_ws) return fail(FOHO_ERR_BAD_ARG, "foho_geo_decode_bwd_rows: null argument");
     if (n_queries >= ((int64_t)1 << 31)) return fail(FOHO_ERR_BAD_ARG, "foho_geo_decode_bwd_rows: row indices are 32-bit");
     if (row_cap <= 0 || row_cap > n_queries) row_cap = n_queries;
-    const Layout l = layout(w, chunk_rows);
+    const Ws o = ws_of(w, chunk_rows, ws);
     const BwdLayout b = bwd_layout(w, chunk_rows);
     const SavedLayout sl = saved_layout(w, chunk_rows);
     const RowsLayout rl = rows_layout(n_queries, row_cap, chunk_rows);
-    if (ws_bytes < l.total || bws_bytes < b.total || rows_ws_bytes < rl.total) return fail(FOHO_ERR_WORKSPACE, "foho_geo_decode_bwd_rows: workspace too small");
+    if (ws_bytes < o.l.total || bws_bytes < b.total || rows_ws_bytes < rl.total) return fail(FOHO_ERR_WORKSPACE, "foho_geo_decode_bwd_rows: workspace too small");
     hipStream_t s = (hipStream_t)stream_;
-    const h16 *kv = (const h16*)((char*)ws + l.kv), *vt = (const h16*)((char*)ws + l.vt);
+    const h16 *kv = o.kv, *vt = o.vt;
     char *base = (char*)bws, *rb = (char*)rows_ws;
     const int W = w->width, Lr = w->n_latents;
     int *counts = (int*)(rb + rl.counts), *mblk = (int*)(rb + rl.mblk), *idx = (int*)(rb + rl.idx);
@@ -3069,24 +2730,19 @@ struct SdpaLayout {
 };
 static SdpaLayout sdpa_layout(int M, int L, int heads) {
     SdpaLayout l{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return o;
-    };
+    Carve cv;
     const size_t W = (size_t)heads * 64;
     l.ldt = (M + 63) & ~63;
-    l.vt = take(W * L * 2);
-    l.kt = take(W * L * 2);
-    l.qs = take(W * (size_t)M * 2);
-    l.qst = take(W * (size_t)l.ldt * 2);
-    l.dot = take(W * (size_t)l.ldt * 2);
-    l.delta = take((size_t)l.ldt * heads * 4);
+    l.vt = cv.bytes(W * L * 2);
+    l.kt = cv.bytes(W * L * 2);
+    l.qs = cv.bytes(W * (size_t)M * 2);
+    l.qst = cv.bytes(W * (size_t)l.ldt * 2);
+    l.dot = cv.bytes(W * (size_t)l.ldt * 2);
+    l.delta = cv.bytes((size_t)l.ldt * heads * 4);
     const int ntiles = (M + 63) / 64, base = std::max(1, (L / 128) * heads);
     l.splits = std::max(1, std::min((1024 + base - 1) / base, ntiles));
-    l.part = take((size_t)l.splits * L * 2 * W * 4);
-    l.total = off;
+    l.part = cv.bytes((size_t)l.splits * L * 2 * W * 4);
+    l.total = cv.off;
     return l;
 }
 static int sdpa_args(const char* who, const foho_sdpa_desc* d, bool bwd) {

@@ -1,4 +1,4 @@
-// Development instrumentation of foho_geo.hip (the counterpart of foho_stamps.h for the step's kernels): the product build defines
+// Development instrumentation of foho_geo.hip and geo_gemm128.inc (the counterpart of foho_stamps.h for the step's kernels): the product build defines
 // none of the switches below and every hook is empty.
 #pragma once
 // The phased GEMM (k_geo_gemm8p).  -DP8_STAMPS: per-wave sums of the K loop's segment durations (shader clocks),
@@ -15,6 +15,7 @@ extern "C" __attribute__((visibility("default"))) void foho_geo_p8_stamps(unsign
     P8_STAMP(0);                                       \
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
 #define P8_STAMP(i) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(ts[i]))
+#define P8_STAMP_TS ts   // (the stamps, for a helper that carries hooks of its own: Tile128::multiply)
 #define P8_ACC()                                                                                           \
     do {                                                                                                   \
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                 \
@@ -31,6 +32,7 @@ extern "C" __attribute__((visibility("default"))) void foho_geo_p8_stamps(unsign
 #else
 #define P8_STAMP_DECL do { } while (0)
 #define P8_STAMP(i) do { } while (0)
+#define P8_STAMP_TS nullptr
 #define P8_ACC() do { } while (0)
 #define P8_STAMP_DUMP(w, nk) do { } while (0)
 #endif

@@ -128,6 +128,41 @@ def test_gemm_kernel_variants_give_the_same_bits(M, N, K, resid):
 
 
 @gpu
+@pytest.mark.parametrize("resid", [False, True])
+@pytest.mark.parametrize("K", [64, 128, 192, 320])
+@pytest.mark.parametrize("M,N", [(95, 128), (130, 256)])
+def test_gemm128_rings_shorter_than_their_depth(M, N, K, resid):
+    """The three 128 x 128 kernels (`gelu | 2` two stages, `| 8` four-deep ring, `| 32` fill + matrix waves) on 1, 2, 3 and 5 K tiles: the
+    four-deep ring's prologue issues fewer than three tiles and its counted waits run their vmcnt(8) / vmcnt(0) tail from the first tile on;
+    a ragged single row tile and a ragged second one.  Finite, within the bound of the tests above against float32 torch (fp16 rounding of
+    the output, 2^-11 relative, with fp32 accumulation of at most 320 products far below it: 2e-3 of the largest magnitude), and equal bit
+    for bit across the three."""
+    L, lib = _lib()
+    g = torch.Generator().manual_seed(M + N + K)
+    A = (torch.randn(M, K, generator=g) * 0.5).half().cuda()
+    W = (torch.randn(N, K, generator=g) / math.sqrt(K)).half().cuda()
+    b = torch.randn(N, generator=g).cuda()
+    R = torch.randn(M, N, generator=g).half().cuda() if resid else None
+    lib.foho_geo_gemm.restype = ctypes.c_int
+    outs = {}
+    for flag in (2, 8, 32):
+        C = torch.full((M, N), float("nan"), dtype=torch.float16, device="cuda")
+        rc = lib.foho_geo_gemm(_p(A), _p(W), _p(b), _p(R) if resid else None, _p(C), M, N, K, flag, ctypes.c_float(1.0),
+                               ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+        assert rc == 0, lib.foho_geo_last_error()
+        torch.cuda.synchronize()
+        outs[flag] = C
+    ref = A.float() @ W.float().T + b
+    if resid:
+        ref = ref.half().float() + R.float()
+    for flag, C in outs.items():
+        assert torch.isfinite(C.float()).all(), flag
+        err = (C.float() - ref).abs().max().item()
+        assert err <= 2e-3 * max(ref.abs().max().item(), 1.0), (flag, err)
+        assert torch.equal(C, outs[2]), flag
+
+
+@gpu
 @pytest.mark.parametrize("M,Lk,heads", [(256, 64, 2), (1000, 256, 4), (700, 3072, 16)])
 def test_attention_against_torch(M, Lk, heads):
     L, lib = _lib()
