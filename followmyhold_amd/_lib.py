@@ -75,7 +75,9 @@ def build(force=False):
     """Compile the HIP library for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     src_dir = os.path.join(_HERE, "csrc")
     srcs = [os.path.join(src_dir, f) for f in os.listdir(src_dir)] + [os.path.join(_HERE, "..", "include", "foho_hip.h")]
-    if force or not os.path.exists(SO_PATH) or any(os.path.getmtime(s) > os.path.getmtime(SO_PATH) for s in srcs):
+    siblings = [os.path.join(_HERE, n) for n in ("libfoho_vol.so", "libfoho_sflexi.so")]      # the same make builds them
+    libs = [SO_PATH] + siblings
+    if force or not all(os.path.exists(p) for p in libs) or max(map(os.path.getmtime, srcs)) > min(map(os.path.getmtime, libs)):
         subprocess.check_call(["make", "-C", src_dir, "-s"])
     return SO_PATH
 

@@ -332,6 +332,11 @@ class HipGeoDecoder:
             return c[2]
         return None
 
+    def drop_grid_cache(self):
+        """Forget the cached query side of the last grid (grid_queries / prepare_queries), so that its buffers can be freed."""
+        self._grid = None
+        self._qcache = None
+
     def grid_queries(self, xyz):
         """The query tensor latent2sdf hands to the decoder for the grid positions `xyz` (N, 3): on the device, rounded to fp16 like
         PL:303, float32, shape (1, N, 3) -- built once per `xyz` tensor (same object, same version) and, when the cached query side fits

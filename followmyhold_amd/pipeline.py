@@ -111,6 +111,19 @@ def final_decode_mode(mode=None):
     return mode
 
 
+FINAL_EXTRACTS = ("dense", "sparse")
+
+
+def final_extract_mode(mode=None):
+    """The final step's extractor: `mode`, else $FOHO_FINAL_EXTRACT, else "dense" (ops.flexicubes on the dense point grid).  "sparse" is
+    sparse_flexi.flexicubes_sparse on per-axis tables: the same mesh bit for bit, and with final_decode="hierarchical" the final
+    dense point grid is never built."""
+    mode = mode if mode is not None else (os.environ.get("FOHO_FINAL_EXTRACT") or "dense")
+    if mode not in FINAL_EXTRACTS:
+        raise E.L.FohoError(f"final_extract {mode!r}: one of {FINAL_EXTRACTS}")
+    return mode
+
+
 def _require_hip_geo(vae):
     hip = getattr(vae, "hip_geo", None)
     if hip is None:
@@ -369,7 +382,7 @@ class GuidedShapePipeline:
     @torch.no_grad()
     def call_batch(self, images, paths, generators=None, guidance_scale=7.5, num_chunks=8000, config=None, renderer=None,
                    J_regressor=None, guidance_octree_resolution=64, final_octree_resolution=384, obj_capacity=None, fovs=None,
-                   final_decode=None, final_decode_min_res=None, guidance_decode=None, guidance_decode_min_res=None):
+                   final_decode=None, final_decode_min_res=None, guidance_decode=None, guidance_decode_min_res=None, final_extract=None):
         """`__call__` for B images at once ("within a GPU, batch the rank's images through each kernel
         launch").  The reference runs its images one after the other (RUN:208-259, batch_size = 1, guid_config.py:9); here
         one pass of the 20-step schedule serves all of them: the DiT and the ShapeVAE transformer run on B latents, the
@@ -393,9 +406,13 @@ class GuidedShapePipeline:
         last step's grid of each image decoded densely or near the surface only (volume.py); per-image stats in stats["final_decode"].
         guidance_decode: "dense" or "hierarchical" (None: $FOHO_GUIDANCE_DECODE, else "dense"), with guidance_decode_min_res, as in
         `__call__`: every decode on the guidance grid by the band decode, all images in lockstep (sdf_band_from_tokens); per-image stats
-        in stats["guidance_decode"]."""
+        in stats["guidance_decode"].
+        final_extract: "dense" or "sparse" (None: $FOHO_FINAL_EXTRACT, else "dense"), as in `__call__`: the last step's mesh of each image
+        by ops.flexicubes on the dense point grid or by flexicubes_sparse on axis tables (the same mesh; with a hierarchical final
+        decode the final point grid is not built); per-image stats in stats["final_extract"]."""
         B = len(images)
         final_mode = final_decode_mode(final_decode)
+        final_sparse = final_extract_mode(final_extract) == "sparse"
         if final_mode == "hierarchical":
             from . import volume
             volume.check_levels(final_octree_resolution, final_decode_min_res)
@@ -581,7 +598,16 @@ class GuidedShapePipeline:
             # the clean-sample estimate as a mesh in the MoGe world (PL:1612-1661): the last one is the result; earlier ones
             # only matter as the fall-back of a later empty decode, so they are taken on the guidance grid
             res = final_octree_resolution if i == n_steps - 1 else guid_res
-            xyz_d, gsz_d = grid(res) if res != guid_res else (xyz_samples, grid_size)
+            sparse = final_sparse and i == n_steps - 1
+            if res == guid_res:
+                xyz_d, gsz_d = xyz_samples, grid_size
+            elif sparse and final_mode == "hierarchical":        # neither the decode nor the extractor reads the dense point grid
+                xyz_d, gsz_d = None, None
+            else:
+                xyz_d, gsz_d = grid(res)
+            if sparse:
+                axes_d = ops.grid_axes(bmin, bmax, res).to(device)
+                stats["final_extract"] = [None] * B
             if i == n_steps - 1 and final_mode == "hierarchical":
                 sdf = final_sdf_hierarchical(self.scheduler.step_final(noise_pred, t, latents), res)
             elif i < n_steps - 1 and guid_band:
@@ -598,7 +624,10 @@ class GuidedShapePipeline:
                     tex_h = torch.zeros_like(hv)
                     tex_h[:, 1] = 1.0
                     hand = Meshes(verts=[hv], faces=[hand_faces[b]], textures=TexturesVertex(verts_features=[tex_h]))
-                verts, faces, _ = ops.flexicubes(xyz_d, sdf[b], res)
+                if sparse:
+                    verts, faces, _, stats["final_extract"][b] = ops.flexicubes_sparse(axes_d, sdf[b], res, return_stats=True)
+                else:
+                    verts, faces, _ = ops.flexicubes(xyz_d, sdf[b], res)
                 if verts.shape[0] == 0:
                     print("Invalid mesh detected, aborting step!")
                 else:
@@ -631,6 +660,8 @@ class GuidedShapePipeline:
             from . import volume
             volume.check_levels(final_res, final_min_res)
             _require_hip_geo(self.vae)
+        # "dense" (default) | "sparse": the final step's extractor (final_extract_mode); not in the signature either
+        final_sparse = final_extract_mode(kwargs.pop("final_extract", None)) == "sparse"
         # "dense" (default) | "hierarchical": how the guidance grid is decoded (latent2sdf_band), with guidance_decode_min_res; not in the
         # signature either
         guid_band = guidance_decode_mode(kwargs.pop("guidance_decode", None)) == "hierarchical"
@@ -714,14 +745,17 @@ class GuidedShapePipeline:
             _tally(stats["guidance_decode"], st)
             return sdf
 
-        def decode_mesh(noise_pred, t, latents, res, xyz, gsz, hierarchical=False, band=False):
+        def decode_mesh(noise_pred, t, latents, res, xyz, gsz, hierarchical=False, band=False, sparse=False):
             x1 = self.scheduler.step_final(noise_pred, t, latents)
-            if hierarchical:          # the final step's grid queried near the surface only; FlexiCubes still on the dense grid
+            if hierarchical:          # the final step's grid queried near the surface only
                 sdf, stats["final_decode"] = latent2sdf_hierarchical(x1, bmin, bmax, res, self.vae, device, min_res=final_min_res)
             elif band:                # a step before the last on the guidance grid
                 sdf = guidance_sdf(x1)
             else:
                 sdf = latent2sdf(x1, xyz, gsz, self.vae, device, num_chunks)
+            if sparse:                # the final step's mesh from axis tables: no dense point grid on the extractor's side
+                v, f, l, stats["final_extract"] = ops.flexicubes_sparse(ops.grid_axes(bmin, bmax, res), sdf[0].flatten(), res, return_stats=True)
+                return v, f, l
             return ops.flexicubes(xyz, sdf[0].flatten(), res)
 
         # Phases B and C re-extract the object from the latent in every iteration (PL:1391-1393, 1507-1509): vertex count,
@@ -884,14 +918,18 @@ class GuidedShapePipeline:
             p = gb.params[0]
             if i >= handopt_start_step:
                 hand_now = similarity_about_center(hand_moge, p[0], p[4:8], p[1:4])
-            if i == num_inference_steps - 1 and final_res != octree_res:     # final decode on the fine grid (PL:1626-1642)
+            last = i == num_inference_steps - 1
+            if last and final_res != octree_res:     # final decode on the fine grid (PL:1626-1642)
                 octree_res = final_res
-                xyz_np, grid_size, _ = generate_dense_grid_points(bmin, bmax, octree_depth=5, octree_resolution=octree_res,
-                                                                  indexing="ij")
-                xyz_samples = torch.as_tensor(xyz_np, dtype=torch.float32, device=device)
+                if final_sparse and final_mode == "hierarchical":     # neither the decode nor the extractor reads the dense point grid
+                    xyz_samples, grid_size = None, [octree_res + 1] * 3
+                else:
+                    xyz_np, grid_size, _ = generate_dense_grid_points(bmin, bmax, octree_depth=5, octree_resolution=octree_res,
+                                                                      indexing="ij")
+                    xyz_samples = torch.as_tensor(xyz_np, dtype=torch.float32, device=device)
             verts, faces, _ = decode_mesh(noise_pred_obj, t, obj_latents, octree_res, xyz_samples, grid_size,
-                                          hierarchical=final_mode == "hierarchical" and i == num_inference_steps - 1,
-                                          band=guid_band and i < num_inference_steps - 1)
+                                          hierarchical=final_mode == "hierarchical" and last, band=guid_band and not last,
+                                          sparse=final_sparse and last)
             if verts.shape[0] == 0:
                 print("Invalid mesh detected, aborting step!")
                 continue

@@ -1,0 +1,115 @@
+"""Sparse FlexiCubes: the mesh of `ops.flexicubes(x_dense, s, res)` from the field and three per-axis coordinate tables.
+
+`ops.flexicubes` wants the dense (res+1)^3 x 3 array of grid positions (685 MB at res 384, built on the host) and a workspace of
+9 B per cube + 8 B per grid edge (1.9 GB at res 384), and walks every cube and edge.  FlexiCubes reads positions only at the corners
+of the cubes whose corners differ in sign.  `flexicubes_sparse` marks those cubes (a bit mask and prefix sums, about 8 MB at res
+384), reads their number back, and extracts on the compact list: the same vertices bit for bit, the same faces and l_dev, in the
+same order.  Work and memory outside the field are proportional to the number of surface cubes.
+
+Two host reads per extraction: the number of surface cubes (it sizes the workspace and the outputs: at most 4 vertices and 6
+triangles per cube, so there is no retry loop), then the vertex and triangle counts.
+
+Forward only: this is the extractor of the no-gradient final step.  The differentiable extractor stays `ops.flexicubes`.
+
+The kernels are libfoho_sflexi.so's (csrc/foho_sflexi.hip, C ABI csrc/foho_sflexi.h).  There is no CPU path: the binding raises
+when the library is missing or of another version.
+"""
+import ctypes
+import os
+
+import numpy as np
+import torch
+
+from ._lib import FohoError, vp
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+SO_PATH = os.path.join(_HERE, "libfoho_sflexi.so")
+VERSION = 100           # FOHO_SFLEXI_VERSION of csrc/foho_sflexi.h
+MAX_RES = 1024          # FOHO_SFLEXI_MAX_RES
+MAX_CUBES = 1 << 26     # FOHO_SFLEXI_MAX_CUBES
+OVER_VERTS, OVER_FACES, OVER_CUBES = 1, 2, 4
+_lib = None
+
+
+def lib():
+    global _lib
+    if _lib is None:
+        if not os.path.exists(SO_PATH):
+            raise FohoError(f"{SO_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` (there is no CPU fallback)")
+        L = ctypes.CDLL(SO_PATH)
+        L.foho_sflexi_version.restype = ctypes.c_int
+        if L.foho_sflexi_version() != VERSION:
+            raise FohoError(f"{SO_PATH} is version {L.foho_sflexi_version()}, this binding is {VERSION}: rebuild (make -C followmyhold_amd/csrc)")
+        L.foho_sflexi_last_error.restype = ctypes.c_char_p
+        i32, sz = ctypes.c_int32, ctypes.c_size_t
+        L.foho_sflexi_mark_bytes.restype, L.foho_sflexi_mark_bytes.argtypes = sz, [i32]
+        L.foho_sflexi_cube_bytes.restype, L.foho_sflexi_cube_bytes.argtypes = sz, [i32]
+        L.foho_sflexi_workspace_bytes.restype, L.foho_sflexi_workspace_bytes.argtypes = sz, [i32, i32]
+        L.foho_sflexi_mark.restype, L.foho_sflexi_mark.argtypes = ctypes.c_int, [vp, i32, vp, sz, vp, vp]
+        L.foho_sflexi_extract.restype = ctypes.c_int
+        L.foho_sflexi_extract.argtypes = [vp, vp, i32, vp, sz, i32, vp, i32, vp, i32, vp, vp, vp, sz, vp]
+        _lib = L
+    return _lib
+
+
+def _check(status, what):
+    if status != 0:
+        raise FohoError(f"{what} failed ({status}): {lib().foho_sflexi_last_error().decode()}")
+
+
+def _p(t):
+    return None if t is None else vp(t.data_ptr())
+
+
+def grid_axes(bbox_min, bbox_max, res):
+    """(3, res+1) float32: per axis the coordinates generate_dense_grid_points gives the grid (numpy float32 linspace), NOT rounded to
+    fp16: the extractor of the dense route gets the unrounded grid (volume.axis_tables rounds, because its tables feed decoder
+    queries)."""
+    return torch.from_numpy(np.stack([np.linspace(bbox_min[k], bbox_max[k], int(res) + 1, dtype=np.float32) for k in range(3)]))
+
+
+def flexicubes_sparse(axes, s, res, return_stats=False):
+    """axes: (3, res+1) float32 (grid_axes); s: (res+1)^3 values, negative inside, in the "ij" layout of generate_dense_grid_points.
+    -> (verts (V,3), faces (F,3) int64, l_dev (V,)) on s's device, equal to ops.flexicubes(x, s, res) for the x those axes mesh to;
+    with return_stats also {"cubes", "vertices", "faces", "workspace_bytes"} (workspace_bytes: mark buffer + cube workspace)."""
+    res = int(res)
+    if not isinstance(s, torch.Tensor) or not s.is_cuda:
+        raise FohoError("flexicubes_sparse needs a CUDA/HIP field (there is no CPU fallback)")
+    if s.requires_grad:
+        raise FohoError("flexicubes_sparse is forward only (the no-gradient final step): a field that requires grad goes through ops.flexicubes")
+    if res < 1 or res > MAX_RES:
+        raise FohoError(f"flexicubes_sparse: resolution {res} outside 1 .. {MAX_RES}")
+    G = res + 1
+    dev = s.device
+    ss = s.detach().to(torch.float32).contiguous().reshape(-1)
+    ax = torch.as_tensor(axes).detach().to(device=dev, dtype=torch.float32).contiguous()
+    if ax.shape != (3, G) or ss.numel() != G ** 3:
+        raise FohoError(f"flexicubes_sparse: expected {(3, G)} axis tables and {G ** 3} SDF values")
+    L = lib()
+    st = vp(torch.cuda.current_stream(dev).cuda_stream)
+    n_marks = L.foho_sflexi_mark_bytes(res)
+    marks = torch.empty(n_marks, dtype=torch.uint8, device=dev)
+    n_dev = torch.empty(1, dtype=torch.int32, device=dev)
+    _check(L.foho_sflexi_mark(_p(ss), res, _p(marks), n_marks, _p(n_dev), st), "foho_sflexi_mark")
+    n = int(n_dev.item())                    # host read 1: the surface cubes size everything below
+    if n > MAX_CUBES:
+        raise FohoError(f"flexicubes_sparse: {n} surface cubes, above {MAX_CUBES}: not a surface (use ops.flexicubes)")
+    stats = {"cubes": n, "vertices": 0, "faces": 0, "workspace_bytes": int(n_marks)}
+    if n == 0:
+        out = (torch.empty(0, 3, device=dev), torch.empty(0, 3, dtype=torch.int64, device=dev), torch.empty(0, device=dev))
+        return out + (stats,) if return_stats else out
+    n_ws = L.foho_sflexi_cube_bytes(n)
+    ws = torch.empty(n_ws, dtype=torch.uint8, device=dev)
+    verts_cap, faces_cap = 4 * n, 6 * n
+    verts = torch.empty(verts_cap, 3, device=dev)
+    faces = torch.empty(faces_cap, 3, dtype=torch.int64, device=dev)
+    ldev = torch.empty(verts_cap, device=dev)
+    counts = torch.empty(3, dtype=torch.int32, device=dev)
+    _check(L.foho_sflexi_extract(_p(ax), _p(ss), res, _p(marks), n_marks, n, _p(verts), verts_cap, _p(faces), faces_cap, _p(ldev),
+                                 _p(counts), _p(ws), n_ws, st), "foho_sflexi_extract")
+    nv, nf, over = counts.tolist()           # host read 2
+    if over:
+        raise FohoError(f"flexicubes_sparse: overflow bits {over} with capacities sized from the cube count ({n} cubes, {nv} vertices, {nf} faces)")
+    stats.update(vertices=nv, faces=nf, workspace_bytes=int(n_marks + n_ws))
+    out = (verts[:nv].clone(), faces[:nf].clone(), ldev[:nv].clone())       # the capacity-sized buffers are not kept alive
+    return out + (stats,) if return_stats else out
