@@ -75,7 +75,7 @@ def build(force=False):
     """Compile the HIP library for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     src_dir = os.path.join(_HERE, "csrc")
     srcs = [os.path.join(src_dir, f) for f in os.listdir(src_dir)] + [os.path.join(_HERE, "..", "include", "foho_hip.h")]
-    siblings = [os.path.join(_HERE, n) for n in ("libfoho_vol.so", "libfoho_sflexi.so")]      # the same make builds them
+    siblings = [os.path.join(_HERE, n) for n in ("libfoho_vol.so", "libfoho_sflexi.so", "libfoho_rastk.so")]      # the same make builds them
     libs = [SO_PATH] + siblings
     if force or not all(os.path.exists(p) for p in libs) or max(map(os.path.getmtime, srcs)) > min(map(os.path.getmtime, libs)):
         subprocess.check_call(["make", "-C", src_dir, "-s"])
@@ -111,3 +111,38 @@ def lib():
 def check(status, what):
     if status != 0:
         raise FohoError(f"{what} failed ({status}): {lib().foho_last_error().decode()}")
+
+
+# ------------------------------------------------------------------------------------------------ libfoho_rastk.so
+RASTK_SO_PATH = os.path.join(_HERE, "libfoho_rastk.so")
+RASTK_VERSION = 100      # FOHO_RASTK_VERSION of csrc/foho_rastk.h
+RASTK_MAX_K = 128        # FOHO_RASTK_MAX_K
+RASTK_CULL_BACKFACES, RASTK_OVER_LIST = 1, 1
+_rastk = None
+
+
+def rastk():
+    """libfoho_rastk.so (C ABI csrc/foho_rastk.h): the K-fragment rasteriser.  No CPU path: raises when the library is missing or
+    of another version."""
+    global _rastk
+    if _rastk is None:
+        if not os.path.exists(RASTK_SO_PATH):
+            raise FohoError(f"{RASTK_SO_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` (there is no CPU fallback)")
+        L = ctypes.CDLL(RASTK_SO_PATH)
+        L.foho_rastk_version.restype = ctypes.c_int
+        if L.foho_rastk_version() != RASTK_VERSION:
+            raise FohoError(f"{RASTK_SO_PATH} is version {L.foho_rastk_version()}, this binding is {RASTK_VERSION}: rebuild (make -C followmyhold_amd/csrc)")
+        L.foho_rastk_last_error.restype = ctypes.c_char_p
+        i64, sz = ctypes.c_int64, ctypes.c_size_t
+        L.foho_rastk_workspace_bytes.restype, L.foho_rastk_workspace_bytes.argtypes = sz, [c_i, c_i, c_i, c_i, c_i, i64]
+        L.foho_rastk_fwd.restype = ctypes.c_int
+        L.foho_rastk_fwd.argtypes = [vp, vp, c_i, c_i, c_i, c_i, c_i, c_f, c_i, vp, vp, vp, vp, vp, vp, i64, vp, sz, vp]
+        L.foho_rastk_bwd.restype = ctypes.c_int
+        L.foho_rastk_bwd.argtypes = [vp, vp, c_i, c_i, c_i, c_i, c_i, vp, vp, vp, vp, vp, c_f, vp]
+        _rastk = L
+    return _rastk
+
+
+def rastk_check(status, what):
+    if status != 0:
+        raise FohoError(f"{what} failed ({status}): {rastk().foho_rastk_last_error().decode()}")

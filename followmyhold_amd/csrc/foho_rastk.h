@@ -1,0 +1,83 @@
+/*
+ * foho_rastk.h -- C ABI of libfoho_rastk.so: the K-fragment rasteriser behind the pytorch3d facade (ops.raster_k_fwd / raster_k,
+ * facade.RasterizationSettings(k_fragments=True)).  A library of its own, next to libfoho_hip.so, libfoho_vol.so and
+ * libfoho_sflexi.so, whose ABIs stay as they are.
+ *
+ * What pytorch3d's rasterize_meshes(faces_per_pixel = K) returns for one mesh, materialised: per pixel the K nearest fragments,
+ * nearest first -- face id, depth, signed squared edge distance, perspective-correct clipped barycentrics -- padded with -1,
+ * with the near-plane clipping (z = znear / 2 = 0.005) and the neighbour rule of MeshRasterizer.  foho_raster_fwd
+ * (include/foho_hip.h) keeps one fragment per pixel in a 64-bit atomicMax plane; this one is pixel parallel over binned faces:
+ *
+ *   setup    one thread per face: NDC gather, near-plane cull / clip, tile box (8x8-pixel tiles) of the blur-inflated pixel box,
+ *            faces per tile (integer atomics)
+ *   scan     exclusive scan of the tile counts; the packed lists need hdr[0] entries
+ *   fill     the per-tile face lists (integer atomics on a cursor; the order inside a list is free, see below)
+ *   select   one wave per tile, one lane per pixel: the tile's faces stream through LDS in chunks of 64, every lane evaluates
+ *            them in the oracle's operation order and keeps the K smallest keys (z bits << 32 | face id << 1 | sub-triangle) in
+ *            an LDS slab; the lane then sorts its keys, re-evaluates the kept fragments and writes the K planes
+ *
+ * The key order (z, face id, sub-triangle) is total, so the selection does not depend on the order faces are visited in: the
+ * forward pass is bitwise repeatable.  Two stated deviations from the naive rasteriser's running buffer:
+ * fragments of exactly equal depth are ordered and cut by (face id, sub-triangle); and of the two halves of a face with one
+ * vertex behind the near plane the one with the smaller |distance| is chosen BEFORE insertion (first half on a tie).
+ *
+ * Conventions: verts_ndc (V,3) float32 rows (x_ndc, y_ndc, z_view), faces (F,3) int32, as foho_raster_fwd; pixel (0,0) is the
+ * top-left one, +X left, +Y up.  Perspective-correct and clipped barycentrics are always on.  Every launch is asynchronous on
+ * the hipStream_t passed as `void* stream`; nothing synchronises and nothing allocates.  Return 0 on success, a negative value
+ * otherwise, with a thread-local message in foho_rastk_last_error().  The forward pass uses integer atomics only; the backward
+ * pass adds with float atomics, like foho_raster_bwd.
+ */
+#ifndef FOHO_RASTK_H
+#define FOHO_RASTK_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#ifndef FOHO_RASTK_API
+#define FOHO_RASTK_API __attribute__((visibility("default")))
+#endif
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define FOHO_RASTK_VERSION 100
+#define FOHO_RASTK_MAX_K 128
+#define FOHO_RASTK_MAX_LIST (1 << 30) /* entries of the packed tile lists */
+/* flags */
+#define FOHO_RASTK_CULL_BACKFACES 1
+/* bits of *overflow */
+#define FOHO_RASTK_OVER_LIST 1 /* the tile lists need more than list_cap entries: no output was written */
+
+FOHO_RASTK_API int foho_rastk_version(void);
+FOHO_RASTK_API const char* foho_rastk_last_error(void);
+
+/* Bytes of workspace for one forward call.  list_cap: capacity of the packed per-tile face lists, in entries (one entry per
+ * (face, 8x8 tile its pixel box overlaps) pair).  0 for an argument out of range: V, F >= 1, F <= 2^30, 1 <= H, W <= 8192,
+ * H W <= 2^25, 1 <= K <= FOHO_RASTK_MAX_K, 0 <= list_cap <= FOHO_RASTK_MAX_LIST. */
+FOHO_RASTK_API size_t foho_rastk_workspace_bytes(int32_t V, int32_t F, int32_t H, int32_t W, int32_t K, int64_t list_cap);
+
+/* pix_to_face: int64 (H,W,K); zbuf, dists: float32 (H,W,K); bary: float32 (H,W,K,3); background entries are -1 in all four.
+ * counts: int32 (H,W), the fragments the pixel received before the cut at K (NULL: not wanted).  overflow: one int32 in device
+ * memory, written by every call.  When bit FOHO_RASTK_OVER_LIST is set no output was written; the first int64 of the workspace
+ * then (and after every call) holds the number of list entries the scene needs: call again with that list_cap.
+ * list_cap is the capacity the workspace was sized for (foho_rastk_workspace_bytes' last argument): the workspace layout depends on
+ * it, so the call takes it explicitly.
+ * K outside 1 .. FOHO_RASTK_MAX_K is an error (-1), not a clamp.  A face with a vertex index outside 0 .. V-1 leaves no fragment. */
+FOHO_RASTK_API int foho_rastk_fwd(const float* verts_ndc, const int32_t* faces, int32_t V, int32_t F, int32_t H, int32_t W, int32_t K,
+                                  float blur_radius, int32_t flags, int64_t* pix_to_face, float* zbuf, float* bary, float* dists,
+                                  int32_t* counts, int32_t* overflow, int64_t list_cap, void* workspace, size_t workspace_bytes,
+                                  void* stream);
+
+/* grad_verts_ndc (V,3) += d(zbuf, bary, dists) / d verts_ndc of every one of the H W K fragments with pix_to_face >= 0: the
+ * per-fragment derivative of foho_raster_bwd (for a face cut by the near plane the barycentric gradient refers to the
+ * sub-triangle's barycentrics, and the cut moves with the vertices).  grad_zbuf, grad_dists: (H,W,K), grad_bary: (H,W,K,3); any
+ * of the three may be NULL.  blur_radius: the forward call's. */
+FOHO_RASTK_API int foho_rastk_bwd(const float* verts_ndc, const int32_t* faces, int32_t V, int32_t F, int32_t H, int32_t W, int32_t K,
+                                  const int64_t* pix_to_face, const float* grad_zbuf, const float* grad_bary, const float* grad_dists,
+                                  float* grad_verts_ndc, float blur_radius, void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

@@ -134,10 +134,14 @@ class BlendParams:
 
 class RasterizationSettings:
     def __init__(self, image_size=256, blur_radius=0.0, faces_per_pixel=1, bin_size=None, max_faces_per_bin=None,
-                 perspective_correct=None, clip_barycentric_coords=None, cull_backfaces=False):
+                 perspective_correct=None, clip_barycentric_coords=None, cull_backfaces=False, k_fragments=False):
         self.image_size = (image_size, image_size) if isinstance(image_size, int) else tuple(image_size)
         self.blur_radius, self.faces_per_pixel = float(blur_radius), int(faces_per_pixel)
         self.bin_size, self.max_faces_per_bin = bin_size, max_faces_per_bin
+        # k_fragments=True: MeshRasterizer returns pytorch3d's (1, H, W, K[, 3]) fragments from the K-fragment rasteriser
+        # (ops.raster_k; 1 <= K <= 128; honours cull_backfaces) and no sil_prod plane.  False (default): one fragment per pixel
+        # plus, for K > 1, the fused silhouette product -- the shapes the guidance path's two renderers are built on.
+        self.k_fragments, self.cull_backfaces = bool(k_fragments), bool(cull_backfaces)
 
 
 class Fragments:
@@ -186,6 +190,10 @@ class MeshRasterizer:
         rs = self.raster_settings
         H, W = rs.image_size
         ndc = self.transform(meshes, **kwargs)
+        if rs.k_fragments:
+            p2f, z, b, d, _ = ops.raster_k(ndc, meshes.faces_packed().contiguous(), H, W, rs.faces_per_pixel, rs.blur_radius,
+                                           rs.cull_backfaces)
+            return Fragments(p2f[None], z[None], b[None], d[None], None)
         want_sil = rs.faces_per_pixel > 1
         # sigma of the silhouette product: the renderer hands over its shader's blend_params.sigma; a bare rasteriser call
         # takes the sigma its blur radius was derived from (blur_radius = log(1 / 1e-4 - 1) sigma, RUN:97)
@@ -252,7 +260,14 @@ class SoftSilhouetteShader(ShaderBase):
 
     def forward(self, fragments, meshes, **kwargs):
         if fragments.sil_prod is None:
-            raise ValueError("SoftSilhouetteShader needs a rasterizer with faces_per_pixel > 1")
+            if fragments.pix_to_face.shape[-1] <= 1:
+                raise ValueError("SoftSilhouetteShader needs a rasterizer with faces_per_pixel > 1")
+            # K-fragment planes (RasterizationSettings(k_fragments=True)): the product over the K layers, in torch
+            blend_params = kwargs.get("blend_params", self.blend_params)
+            mask = fragments.pix_to_face >= 0
+            a = 1.0 - torch.prod(1.0 - torch.sigmoid(-fragments.dists / blend_params.sigma) * mask, dim=-1)
+            rgb = torch.ones(a.shape + (3,), device=a.device, dtype=a.dtype)
+            return torch.cat([rgb, a[..., None]], dim=-1)
         a = (1.0 - fragments.sil_prod)
         rgb = torch.ones(a.shape + (3,), device=a.device, dtype=a.dtype)
         return torch.cat([rgb, a[..., None]], dim=-1)

@@ -80,6 +80,103 @@ def raster_sil_bwd(verts_ndc, faces, sil_prod, grad_prod, blur_radius, sigma):
     return g
 
 
+# ------------------------------------------------------------------------------------------------ K-fragment rasteriser
+def _raster_k_args(verts_ndc, faces, H, W, K):
+    """Argument checks of raster_k_fwd / raster_k_bwd, before any device work."""
+    K, H, W = int(K), int(H), int(W)
+    if K < 1 or K > L.RASTK_MAX_K:
+        raise ValueError(f"raster_k: K = {K} outside 1 .. {L.RASTK_MAX_K} (not clamped)")
+    if H < 1 or W < 1 or H > 8192 or W > 8192 or H * W > (1 << 25):
+        raise ValueError(f"raster_k: frame {H} x {W} out of range")
+    if verts_ndc.dim() != 2 or verts_ndc.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3 or not len(verts_ndc) or not len(faces):
+        raise ValueError("raster_k: expected (V,3) vertices and (F,3) faces")
+    if faces.dtype not in (torch.int32, torch.int64) or not faces.is_contiguous():
+        raise ValueError("raster_k: faces must be a contiguous int32 or int64 tensor")
+    _need_cuda(verts_ndc, faces)
+    return K, H, W
+
+
+def raster_k_fwd(verts_ndc, faces, H, W, K, blur_radius, cull_backfaces=False, list_cap=None):
+    """pytorch3d rasterize_meshes(faces_per_pixel=K) for one mesh, materialised (libfoho_rastk.so; 1 <= K <= 128).
+    Returns dict(pix_to_face (H,W,K) int64, zbuf (H,W,K), bary (H,W,K,3), dists (H,W,K), counts (H,W) int32 [fragments the pixel
+    received before the cut at K]); background entries are -1.  list_cap: capacity of the per-tile face lists in entries; when
+    the scene needs more, the call is repeated once with the exact size (`retried` in the result says so)."""
+    K, H, W = _raster_k_args(verts_ndc, faces, H, W, K)
+    lib = L.rastk()
+    v, f = _f32(verts_ndc), faces.detach().to(torch.int32)
+    V, F = v.shape[0], f.shape[0]
+    dev = v.device
+    cap = int(list_cap) if list_cap is not None else max(4 * F, 1024)
+    p2f = torch.empty(H, W, K, dtype=torch.int64, device=dev)
+    zb, di = torch.empty(H, W, K, device=dev), torch.empty(H, W, K, device=dev)
+    ba = torch.empty(H, W, K, 3, device=dev)
+    cn = torch.empty(H, W, dtype=torch.int32, device=dev)
+    ov = torch.zeros(1, dtype=torch.int32, device=dev)
+    flags = L.RASTK_CULL_BACKFACES if cull_backfaces else 0
+    retried = False
+    while True:
+        nws = lib.foho_rastk_workspace_bytes(V, F, H, W, K, cap)
+        if nws == 0:
+            raise L.FohoError(f"raster_k_fwd: no workspace size for V={V} F={F} H={H} W={W} K={K} list_cap={cap}")
+        ws = torch.empty(nws, dtype=torch.uint8, device=dev)
+        L.rastk_check(lib.foho_rastk_fwd(P(v.data_ptr()), P(f.data_ptr()), V, F, H, W, K, float(blur_radius), flags, P(p2f.data_ptr()),
+                                         P(zb.data_ptr()), P(ba.data_ptr()), P(di.data_ptr()), P(cn.data_ptr()), P(ov.data_ptr()), cap,
+                                         P(ws.data_ptr()), nws, _stream(v)), "foho_rastk_fwd")
+        if not (int(ov.item()) & L.RASTK_OVER_LIST):      # one host read per call: the list size is data dependent
+            break
+        if retried:
+            raise L.FohoError("raster_k_fwd: the tile lists overflowed again at the size the first pass reported")
+        cap, retried = int(ws[:8].view(torch.int64).item()), True
+    return dict(pix_to_face=p2f, zbuf=zb, bary=ba, dists=di, counts=cn, retried=retried, list_cap=cap, workspace_bytes=int(nws))
+
+
+def raster_k_bwd(verts_ndc, faces, pix_to_face, grad_zbuf=None, grad_bary=None, grad_dists=None, blur_radius=0.0):
+    """Backward of all H W K fragments of raster_k_fwd -> grad w.r.t. verts_ndc (V,3).  pix_to_face: (H,W,K); any of the three
+    gradients may be None.  blur_radius: the forward call's."""
+    if pix_to_face.dim() != 3 or pix_to_face.dtype != torch.int64:
+        raise ValueError("raster_k_bwd: pix_to_face must be (H,W,K) int64")
+    H, W, K = pix_to_face.shape
+    _raster_k_args(verts_ndc, faces, H, W, K)
+    lib = L.rastk()
+    v, f = _f32(verts_ndc), faces.detach().to(torch.int32)
+    g = torch.zeros_like(v)
+    gz = _f32(grad_zbuf) if grad_zbuf is not None else None
+    gb = _f32(grad_bary) if grad_bary is not None else None
+    gd = _f32(grad_dists) if grad_dists is not None else None
+    for t, shape in ((gz, (H, W, K)), (gb, (H, W, K, 3)), (gd, (H, W, K))):
+        if t is not None and tuple(t.shape) != shape:
+            raise ValueError(f"raster_k_bwd: gradient of shape {tuple(t.shape)}, expected {shape}")
+    p2f = pix_to_face.contiguous()
+    L.rastk_check(lib.foho_rastk_bwd(P(v.data_ptr()), P(f.data_ptr()), v.shape[0], f.shape[0], H, W, K, P(p2f.data_ptr()),
+                                     P(gz.data_ptr()) if gz is not None else None, P(gb.data_ptr()) if gb is not None else None,
+                                     P(gd.data_ptr()) if gd is not None else None, P(g.data_ptr()), float(blur_radius), _stream(v)),
+                  "foho_rastk_bwd")
+    return g
+
+
+class _RasterKFn(torch.autograd.Function):
+    """raster_k_fwd / raster_k_bwd as one differentiable operator (w.r.t. verts_ndc)."""
+
+    @staticmethod
+    def forward(ctx, verts_ndc, faces, H, W, K, blur_radius, cull_backfaces):
+        out = raster_k_fwd(verts_ndc, faces, H, W, K, blur_radius, cull_backfaces)
+        ctx.blur = float(blur_radius)
+        ctx.save_for_backward(verts_ndc.detach(), faces, out["pix_to_face"])
+        ctx.mark_non_differentiable(out["pix_to_face"], out["counts"])
+        return out["pix_to_face"], out["zbuf"], out["bary"], out["dists"], out["counts"]
+
+    @staticmethod
+    def backward(ctx, _gp, g_z, g_b, g_d, _gc):
+        v, f, p2f = ctx.saved_tensors
+        g = raster_k_bwd(v, f, p2f, g_z, g_b, g_d, blur_radius=ctx.blur)
+        return g.to(v.dtype), None, None, None, None, None, None
+
+
+def raster_k(verts_ndc, faces, H, W, K, blur_radius, cull_backfaces=False):
+    """(pix_to_face, zbuf, bary, dists, counts) of raster_k_fwd, differentiable w.r.t. verts_ndc."""
+    return _RasterKFn.apply(verts_ndc, faces, int(H), int(W), int(K), float(blur_radius), bool(cull_backfaces))
+
+
 # ------------------------------------------------------------------------------------------------ knn / sdf
 def knn1(p1, p2):
     """pytorch3d.ops.knn_points(K=1): (squared distances (N1,), indices (N1,) int64)."""
