@@ -71,12 +71,20 @@ N_KERNELS = 10
 ABI_VERSION = 105     # 105 = foho_vae_fwd / _bwd, foho_geo_weights.flags, foho_geo_gemm variant bits, FOHO_API visibility; 104 = foho_geo_weights.ln_{q,kv,2}_eps, foho_geo_decode_bwd_rows, foho_geo_prepare_queries / _decode_fwd_cached; include/foho_hip.h: 102 = foho_step_cfg.listed_cap, foho_step_desc.hand_order_valid, foho_abi_sizes; 103 = foho_geo_weights.q_norm / k_norm, foho_geo_abi_size
 
 
+# the side libraries: libfoho_<name>.so exports foho_<name>_* (C ABI csrc/foho_<name>.h) and is of version FOHO_<NAME>_VERSION
+SIDE_VERSIONS = {"vol": 100, "sflexi": 100, "rastk": 100}
+_sides = {}
+
+
+def side_path(name):
+    return os.path.join(_HERE, f"libfoho_{name}.so")
+
+
 def build(force=False):
     """Compile the HIP library for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     src_dir = os.path.join(_HERE, "csrc")
     srcs = [os.path.join(src_dir, f) for f in os.listdir(src_dir)] + [os.path.join(_HERE, "..", "include", "foho_hip.h")]
-    siblings = [os.path.join(_HERE, n) for n in ("libfoho_vol.so", "libfoho_sflexi.so", "libfoho_rastk.so")]      # the same make builds them
-    libs = [SO_PATH] + siblings
+    libs = [SO_PATH] + [side_path(n) for n in SIDE_VERSIONS]      # the same make builds them
     if force or not all(os.path.exists(p) for p in libs) or max(map(os.path.getmtime, srcs)) > min(map(os.path.getmtime, libs)):
         subprocess.check_call(["make", "-C", src_dir, "-s"])
     return SO_PATH
@@ -90,6 +98,7 @@ def lib():
                             "(there is no CPU fallback)")
         L = ctypes.CDLL(SO_PATH)
         L.foho_last_error.restype = ctypes.c_char_p
+        L.foho_geo_last_error.restype = ctypes.c_char_p
         L.foho_version.restype = ctypes.c_int
         sizes = (ctypes.c_int64 * 5)()
         L.foho_abi_sizes.restype = ctypes.c_int
@@ -113,36 +122,66 @@ def check(status, what):
         raise FohoError(f"{what} failed ({status}): {lib().foho_last_error().decode()}")
 
 
+def geo_error():
+    """Last error of the foho_geo_* / foho_vae_* / foho_sdpa_* entry points (csrc/foho_geo.hip keeps its own string)."""
+    return lib().foho_geo_last_error().decode()
+
+
+def geo_check(status, what):
+    if status != 0:
+        raise FohoError(f"{what} failed ({status}): {geo_error()}")
+
+
+def load_side(name, signatures):
+    """libfoho_<name>.so with `signatures` ({function: (restype, argtypes)}) set.  No CPU path: raises when the library is missing or
+    of another version."""
+    L = _sides.get(name)
+    if L is None:
+        path, version = side_path(name), SIDE_VERSIONS[name]
+        if not os.path.exists(path):
+            raise FohoError(f"{path} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` (there is no CPU fallback)")
+        L = ctypes.CDLL(path)
+        ver = getattr(L, f"foho_{name}_version")
+        ver.restype = ctypes.c_int
+        if ver() != version:
+            raise FohoError(f"{path} is version {ver()}, this binding is {version}: rebuild (make -C followmyhold_amd/csrc)")
+        getattr(L, f"foho_{name}_last_error").restype = ctypes.c_char_p
+        for fn, (restype, argtypes) in signatures.items():
+            f = getattr(L, fn)
+            f.restype, f.argtypes = restype, argtypes
+        _sides[name] = L
+    return L
+
+
+def check_side(lib, prefix, status, what):
+    if status != 0:
+        raise FohoError(f"{what} failed ({status}): {getattr(lib, prefix + '_last_error')().decode()}")
+
+
+def _p(t):
+    return None if t is None else vp(t.data_ptr())
+
+
+def _stream(device):
+    import torch
+    return vp(torch.cuda.current_stream(device).cuda_stream)
+
+
 # ------------------------------------------------------------------------------------------------ libfoho_rastk.so
-RASTK_SO_PATH = os.path.join(_HERE, "libfoho_rastk.so")
-RASTK_VERSION = 100      # FOHO_RASTK_VERSION of csrc/foho_rastk.h
+RASTK_SO_PATH = side_path("rastk")
+RASTK_VERSION = SIDE_VERSIONS["rastk"]      # FOHO_RASTK_VERSION of csrc/foho_rastk.h
 RASTK_MAX_K = 128        # FOHO_RASTK_MAX_K
 RASTK_CULL_BACKFACES, RASTK_OVER_LIST = 1, 1
-_rastk = None
+_RASTK_SIGNATURES = {
+    "foho_rastk_workspace_bytes": (ctypes.c_size_t, [c_i, c_i, c_i, c_i, c_i, ctypes.c_int64]),
+    "foho_rastk_fwd": (ctypes.c_int, [vp, vp, c_i, c_i, c_i, c_i, c_i, c_f, c_i, vp, vp, vp, vp, vp, vp, ctypes.c_int64, vp, ctypes.c_size_t, vp]),
+    "foho_rastk_bwd": (ctypes.c_int, [vp, vp, c_i, c_i, c_i, c_i, c_i, vp, vp, vp, vp, vp, c_f, vp])}
 
 
 def rastk():
-    """libfoho_rastk.so (C ABI csrc/foho_rastk.h): the K-fragment rasteriser.  No CPU path: raises when the library is missing or
-    of another version."""
-    global _rastk
-    if _rastk is None:
-        if not os.path.exists(RASTK_SO_PATH):
-            raise FohoError(f"{RASTK_SO_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` (there is no CPU fallback)")
-        L = ctypes.CDLL(RASTK_SO_PATH)
-        L.foho_rastk_version.restype = ctypes.c_int
-        if L.foho_rastk_version() != RASTK_VERSION:
-            raise FohoError(f"{RASTK_SO_PATH} is version {L.foho_rastk_version()}, this binding is {RASTK_VERSION}: rebuild (make -C followmyhold_amd/csrc)")
-        L.foho_rastk_last_error.restype = ctypes.c_char_p
-        i64, sz = ctypes.c_int64, ctypes.c_size_t
-        L.foho_rastk_workspace_bytes.restype, L.foho_rastk_workspace_bytes.argtypes = sz, [c_i, c_i, c_i, c_i, c_i, i64]
-        L.foho_rastk_fwd.restype = ctypes.c_int
-        L.foho_rastk_fwd.argtypes = [vp, vp, c_i, c_i, c_i, c_i, c_i, c_f, c_i, vp, vp, vp, vp, vp, vp, i64, vp, sz, vp]
-        L.foho_rastk_bwd.restype = ctypes.c_int
-        L.foho_rastk_bwd.argtypes = [vp, vp, c_i, c_i, c_i, c_i, c_i, vp, vp, vp, vp, vp, c_f, vp]
-        _rastk = L
-    return _rastk
+    """libfoho_rastk.so (C ABI csrc/foho_rastk.h): the K-fragment rasteriser."""
+    return load_side("rastk", _RASTK_SIGNATURES)
 
 
 def rastk_check(status, what):
-    if status != 0:
-        raise FohoError(f"{what} failed ({status}): {rastk().foho_rastk_last_error().decode()}")
+    check_side(rastk(), "foho_rastk", status, what)

@@ -34,6 +34,7 @@
 #include <stdlib.h>
 
 #include "../../include/foho_hip.h"
+#include "foho_carve.h"
 #include "foho_geo_stamps.h"
 
 namespace geo {
@@ -2201,16 +2202,6 @@ static int check_weights(const foho_geo_weights* w) {
     return FOHO_OK;
 }
 
-// Bump allocator of the workspace layouts: byte offsets, every block rounded up to 256 bytes; `off` ends as the total.
-struct Carve {
-    size_t off = 0;
-    size_t bytes(size_t n) {
-        const size_t o = off;
-        off += (n + 255) & ~(size_t)255;
-        return o;
-    }
-};
-
 struct Layout {
     size_t kv, vt, e, a, b, c, h, w1f, fold1, fold2, stats, rowstat, total;
 };
@@ -2218,21 +2209,21 @@ static Layout layout(const foho_geo_weights* w, int chunk) {
     Layout l{};
     Carve cv;
     const size_t W = w->width, F = w->hidden, C = chunk, Lr = w->n_latents, rows = std::max<size_t>(chunk, Lr);  // the prepare step normalises the latents in buffer A
-    l.kv = cv.bytes(Lr * 2 * W * 2);
-    l.vt = cv.bytes(W * Lr * 2);
+    l.kv = cv.take(Lr * 2 * W * 2);
+    l.vt = cv.take(W * Lr * 2);
     // LayerNorm folded into the forward GEMMs (chain_latent_side): fc1's weights with ln_2's gain and the folded vectors -- like kv / vt
     // written by the prepare step, at offsets that do not depend on the chunk
-    l.w1f = cv.bytes(F * W * 2);
-    l.fold1 = cv.bytes(2 * F * 4);               // 2 hidden floats
-    l.fold2 = cv.bytes((2 * W + 4) * 4);         // 2 W + 2 floats, in room for 2 W + 4
-    l.e = cv.bytes(C * 64 * 2);
-    l.a = cv.bytes(rows * W * 2);
-    l.b = cv.bytes(C * W * 2);
-    l.c = cv.bytes(C * W * 2);
-    l.h = cv.bytes(C * F * 2);
+    l.w1f = cv.take(F * W * 2);
+    l.fold1 = cv.take(2 * F * 4);               // 2 hidden floats
+    l.fold2 = cv.take((2 * W + 4) * 4);         // 2 W + 2 floats, in room for 2 W + 4
+    l.e = cv.take(C * 64 * 2);
+    l.a = cv.take(rows * W * 2);
+    l.b = cv.take(C * W * 2);
+    l.c = cv.take(C * W * 2);
+    l.h = cv.take(C * F * 2);
     // ... the per-row statistics of the folded LayerNorms (16 parts of 4 floats at width 1024) and (rstd, rstd mean) per row
-    l.stats = cv.bytes(C * (W / 64) * 4 * 4);    // chunk x parts x 4 floats
-    l.rowstat = cv.bytes(C * 2 * 4);             // chunk x 2 floats
+    l.stats = cv.take(C * (W / 64) * 4 * 4);    // chunk x parts x 4 floats
+    l.rowstat = cv.take(C * 2 * 4);             // chunk x 2 floats
     l.total = cv.off;
     return l;
 }
@@ -2478,22 +2469,22 @@ static BwdLayout bwd_layout(const foho_geo_weights* w, int chunk) {
     Carve cv;
     const size_t W = w->width, F = w->hidden, C = chunk;
     l.ldt = (chunk + 63) & ~63;
-    l.e = cv.bytes(C * 64 * 2);
-    l.x0 = cv.bytes(C * W * 2);
-    l.xn = cv.bytes(C * W * 2);
-    l.qs = cv.bytes(C * W * 2);
-    l.qst = cv.bytes(W * (size_t)l.ldt * 2);
-    l.at = cv.bytes(C * W * 2);
-    l.x1 = cv.bytes(C * W * 2);
-    l.z = cv.bytes(C * F * 2);
-    l.h = cv.bytes(C * F * 2);
-    l.x2 = cv.bytes(C * W * 2);
-    l.dx2 = cv.bytes(C * W * 2);
-    l.dat = cv.bytes(W * (size_t)l.ldt * 2);
-    l.lse = cv.bytes((size_t)l.ldt * w->heads * 4);    // rows up to the next multiple of 64: the padding of the last query tile
-    l.delta = cv.bytes((size_t)l.ldt * w->heads * 4);
+    l.e = cv.take(C * 64 * 2);
+    l.x0 = cv.take(C * W * 2);
+    l.xn = cv.take(C * W * 2);
+    l.qs = cv.take(C * W * 2);
+    l.qst = cv.take(W * (size_t)l.ldt * 2);
+    l.at = cv.take(C * W * 2);
+    l.x1 = cv.take(C * W * 2);
+    l.z = cv.take(C * F * 2);
+    l.h = cv.take(C * F * 2);
+    l.x2 = cv.take(C * W * 2);
+    l.dx2 = cv.take(C * W * 2);
+    l.dat = cv.take(W * (size_t)l.ldt * 2);
+    l.lse = cv.take((size_t)l.ldt * w->heads * 4);    // rows up to the next multiple of 64: the padding of the last query tile
+    l.delta = cv.take((size_t)l.ldt * w->heads * 4);
     l.splits = bwd_splits(w, chunk);
-    l.part = cv.bytes((size_t)l.splits * w->n_latents * 2 * W * 4);
+    l.part = cv.take((size_t)l.splits * w->n_latents * 2 * W * 4);
     l.total = cv.off;
     return l;
 }
@@ -2524,13 +2515,13 @@ static SavedLayout saved_layout(const foho_geo_weights* w, int chunk) {
     SavedLayout l{};
     Carve cv;
     const size_t W = w->width, F = w->hidden, C = chunk, ldt = (chunk + 63) & ~63;
-    l.qs = cv.bytes(C * W * 2);
-    l.qst = cv.bytes(W * ldt * 2);
-    l.at = cv.bytes(C * W * 2);
-    l.x1 = cv.bytes(C * W * 2);
-    l.z = cv.bytes(C * F * 2);
-    l.x2 = cv.bytes(C * W * 2);
-    l.lse = cv.bytes(ldt * (size_t)w->heads * 4);
+    l.qs = cv.take(C * W * 2);
+    l.qst = cv.take(W * ldt * 2);
+    l.at = cv.take(C * W * 2);
+    l.x1 = cv.take(C * W * 2);
+    l.z = cv.take(C * F * 2);
+    l.x2 = cv.take(C * W * 2);
+    l.lse = cv.take(ldt * (size_t)w->heads * 4);
     l.total = cv.off;
     return l;
 }
@@ -2665,11 +2656,11 @@ static RowsLayout rows_layout(int64_t n, int64_t cap, int chunk) {
     Carve cv;
     l.nscan = (int)((n + ROWS_PER_WG - 1) / ROWS_PER_WG);
     l.nblk = (int)std::max<int64_t>((cap + chunk - 1) / chunk, 1);
-    l.counts = cv.bytes((size_t)std::max(l.nscan, 1) * 4);
-    l.mblk = cv.bytes((size_t)(std::max(l.nblk, 1) + 2) * 4);     // [0]: the count, [1]: rows dropped for lack of capacity, [2 + c]: rows of block c
-    l.q = cv.bytes((size_t)std::max<int64_t>(cap, 1) * 12);
-    l.g = cv.bytes((size_t)std::max<int64_t>(cap, 1) * 4);
-    l.idx = cv.bytes((size_t)std::max<int64_t>(cap, 1) * 4);
+    l.counts = cv.take((size_t)std::max(l.nscan, 1) * 4);
+    l.mblk = cv.take((size_t)(std::max(l.nblk, 1) + 2) * 4);     // [0]: the count, [1]: rows dropped for lack of capacity, [2 + c]: rows of block c
+    l.q = cv.take((size_t)std::max<int64_t>(cap, 1) * 12);
+    l.g = cv.take((size_t)std::max<int64_t>(cap, 1) * 4);
+    l.idx = cv.take((size_t)std::max<int64_t>(cap, 1) * 4);
     l.total = cv.off;
     return l;
 }
@@ -2733,15 +2724,15 @@ static SdpaLayout sdpa_layout(int M, int L, int heads) {
     Carve cv;
     const size_t W = (size_t)heads * 64;
     l.ldt = (M + 63) & ~63;
-    l.vt = cv.bytes(W * L * 2);
-    l.kt = cv.bytes(W * L * 2);
-    l.qs = cv.bytes(W * (size_t)M * 2);
-    l.qst = cv.bytes(W * (size_t)l.ldt * 2);
-    l.dot = cv.bytes(W * (size_t)l.ldt * 2);
-    l.delta = cv.bytes((size_t)l.ldt * heads * 4);
+    l.vt = cv.take(W * L * 2);
+    l.kt = cv.take(W * L * 2);
+    l.qs = cv.take(W * (size_t)M * 2);
+    l.qst = cv.take(W * (size_t)l.ldt * 2);
+    l.dot = cv.take(W * (size_t)l.ldt * 2);
+    l.delta = cv.take((size_t)l.ldt * heads * 4);
     const int ntiles = (M + 63) / 64, base = std::max(1, (L / 128) * heads);
     l.splits = std::max(1, std::min((1024 + base - 1) / base, ntiles));
-    l.part = cv.bytes((size_t)l.splits * L * 2 * W * 4);
+    l.part = cv.take((size_t)l.splits * L * 2 * W * 4);
     l.total = cv.off;
     return l;
 }

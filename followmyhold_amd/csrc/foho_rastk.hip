@@ -14,31 +14,21 @@
 // Compiled with foho_step.hip's flags (-ffp-contract=off, correctly rounded division and sqrt): the per-(pixel, face) arithmetic is
 // foho_common.h's eval_frag / clip_subtris / subtri_bary_to_face, the functions k_raster.inc's evaluate stage and k_raster_export
 // call, and that arithmetic decides face ids.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+// The error plumbing and the workgroup scan are foho_side.h's; the workspace allocator is foho_carve.h's.
 #include <math.h>
-#include <string>
 
+#include "foho_carve.h"
 #include "foho_common.h"
 #include "foho_rastk.h"
+#include "foho_side.h"
 
 namespace {
 
 using namespace foho;
 
-thread_local std::string g_err;
-
-int fail(int code, const std::string& msg) {
-    g_err = msg;
-    return code;
-}
-
-constexpr int TPB = 256;
 constexpr int TILE = 8;          // 8x8 pixels = one wave
 constexpr int CH = 64;           // faces per LDS chunk of k_rk_select
 constexpr float Z_CLIP = 0.01f * 0.5f;  // znear / 2 of the path's camera, as foho_raster_fwd / _bwd
-
-size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct Hdr {
     long long need;  // list entries the scene needs
@@ -62,20 +52,15 @@ Ws carve(const void* ws, int F, int H, int W, long long list_cap) {
     w.tiles_x = (W + TILE - 1) / TILE, w.tiles_y = (H + TILE - 1) / TILE;
     w.tiles = (size_t)w.tiles_x * w.tiles_y;
     char* p = (char*)const_cast<void*>(ws);
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        const size_t r = o;
-        o = al(o + bytes);
-        return r;
-    };
-    w.hdr = (Hdr*)(p + take(sizeof(Hdr)));
-    w.face_ndc = (float*)(p + take((size_t)F * 9 * 4));
-    w.tbox = (ushort4*)(p + take((size_t)F * sizeof(ushort4)));
-    w.tcount = (unsigned*)(p + take(w.tiles * 4));
-    w.toff = (unsigned*)(p + take((w.tiles + 1) * 4));
-    w.cursor = (unsigned*)(p + take(w.tiles * 4));
-    w.list = (int*)(p + take((size_t)list_cap * 4));
-    w.bytes = o;
+    Carve cv;
+    w.hdr = (Hdr*)(p + cv.take(sizeof(Hdr)));
+    w.face_ndc = (float*)(p + cv.take((size_t)F * 9 * 4));
+    w.tbox = (ushort4*)(p + cv.take((size_t)F * sizeof(ushort4)));
+    w.tcount = (unsigned*)(p + cv.take(w.tiles * 4));
+    w.toff = (unsigned*)(p + cv.take((w.tiles + 1) * 4));
+    w.cursor = (unsigned*)(p + cv.take(w.tiles * 4));
+    w.list = (int*)(p + cv.take((size_t)list_cap * 4));
+    w.bytes = cv.off;
     return w;
 }
 
@@ -157,14 +142,7 @@ __global__ __launch_bounds__(TPB) void k_rk_scan(const unsigned* __restrict__ tc
     const long long b = min((long long)t * seg, tiles), e = min(b + seg, tiles);
     unsigned long long s = 0;
     for (long long i = b; i < e; i++) s += tcount[i];
-    s_sum[t] = s;
-    __syncthreads();
-    for (int d = 1; d < TPB; d <<= 1) {
-        const unsigned long long add = (t >= d) ? s_sum[t - d] : 0ull;
-        __syncthreads();
-        s_sum[t] += add;
-        __syncthreads();
-    }
+    const unsigned long long before = block_exclusive_scan<TPB>(s, s_sum);
     const unsigned long long total = s_sum[TPB - 1];
     const bool over = total > (unsigned long long)list_cap;
     if (t == 0) {
@@ -174,7 +152,7 @@ __global__ __launch_bounds__(TPB) void k_rk_scan(const unsigned* __restrict__ tc
         *overflow = over ? FOHO_RASTK_OVER_LIST : 0;
     }
     if (over) return;
-    unsigned run = (unsigned)(s_sum[t] - s);
+    unsigned run = (unsigned)before;
     for (long long i = b; i < e; i++) {
         toff[i] = run;
         cursor[i] = run;
@@ -343,14 +321,6 @@ __global__ __launch_bounds__(TPB) void k_rk_bwd(const float* __restrict__ verts,
             if (gv[3 * k + q] != 0.f) atomicAdd(&g_verts[3 * (size_t)vi[k] + q], gv[3 * k + q]);
 }
 
-unsigned blocks_for(size_t n, int per) { return (unsigned)(n ? (n + per - 1) / per : 1); }
-
-int launched(const char* what) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(-2, std::string(what) + ": launch failed: " + hipGetErrorString(e));
-    return 0;
-}
-
 bool dims_ok(int32_t V, int32_t F, int32_t H, int32_t W) {
     return V >= 1 && F >= 1 && F <= (1 << 30) && H >= 1 && W >= 1 && H <= 8192 && W <= 8192 && (size_t)H * W <= ((size_t)1 << 25);
 }
@@ -359,11 +329,9 @@ bool cap_ok(int64_t c) { return c >= 0 && c <= FOHO_RASTK_MAX_LIST; }
 
 }  // namespace
 
+FOHO_SIDE_ENTRY_POINTS(rastk, FOHO_RASTK_API, FOHO_RASTK_VERSION)
+
 extern "C" {
-
-FOHO_RASTK_API int foho_rastk_version(void) { return FOHO_RASTK_VERSION; }
-
-FOHO_RASTK_API const char* foho_rastk_last_error(void) { return g_err.c_str(); }
 
 FOHO_RASTK_API size_t foho_rastk_workspace_bytes(int32_t V, int32_t F, int32_t H, int32_t W, int32_t K, int64_t list_cap) {
     if (!dims_ok(V, F, H, W) || !k_ok(K) || !cap_ok(list_cap)) return 0;

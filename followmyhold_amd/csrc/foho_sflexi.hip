@@ -16,28 +16,19 @@
 //                   (cube, patch), quad offsets by (axis, i, j, k): the dense orders.  off[n] is the vertex total
 //   k_sf_emit       vertices per surface cube (positions from the tables), quads per (axis, surface cube), the four ring cubes
 //                   through rank()
-// Compiled with foho_step.hip's flags (-ffp-contract=off, correctly rounded division and sqrt): the vertex arithmetic below restates
-// flexi_verts_role (k_flexi.inc) expression for expression, which is what makes the vertices and l_dev bitwise the dense ones.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <string>
-
+// Compiled with foho_step.hip's flags (-ffp-contract=off, correctly rounded division and sqrt): the sign code, the dual vertex and
+// l_dev, the ring table and the quad's orientation and split are flexi_core.h's functions, the ones k_flexi.inc calls, which is what
+// makes the vertices, faces and l_dev bitwise the dense ones.  What is written here is what differs: corner positions from the axis
+// tables, offsets and case codes through rank_of on the compact list, the orientation from the case code, the capacity checks.
+// The error plumbing, gid, the workgroup scan and the mask-word helpers are foho_side.h's; the workspace allocator is foho_carve.h's.
+#include "flexi_core.h"
+#include "foho_carve.h"
+#include "foho_side.h"
 #include "foho_sflexi.h"
-#include "k_flexi_tables.inc"
 
 namespace {
 
-thread_local std::string g_err;
-
-int fail(int code, const std::string& msg) {
-    g_err = msg;
-    return code;
-}
-
-constexpr int TPB = 256;
 constexpr int ITEMS = 2048;  // items per workgroup of the scan (256 threads x 8)
-
-size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct MarkWs {
     uint64_t* mask;  // words: bit c % 64 of word c / 64 for cube c
@@ -51,17 +42,12 @@ MarkWs carve_mark(const void* ws, int res) {
     MarkWs w;
     w.words = (C + 63) / 64, w.blocks = (C + TPB - 1) / TPB, w.chunks = (w.blocks + ITEMS - 1) / ITEMS;
     char* p = (char*)const_cast<void*>(ws);
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        const size_t r = o;
-        o = al(o + bytes);
-        return r;
-    };
-    w.mask = (uint64_t*)(p + take(w.words * 8));
-    w.bpre = (int32_t*)(p + take(w.blocks * 4));
-    w.csum = (int32_t*)(p + take(w.chunks * 4));
-    w.total = (int32_t*)(p + take(4));
-    w.bytes = o;
+    Carve cv;
+    w.mask = (uint64_t*)(p + cv.take(w.words * 8));
+    w.bpre = (int32_t*)(p + cv.take(w.blocks * 4));
+    w.csum = (int32_t*)(p + cv.take(w.chunks * 4));
+    w.total = (int32_t*)(p + cv.take(4));
+    w.bytes = cv.off;
     return w;
 }
 
@@ -79,34 +65,15 @@ CubeWs carve_cube(void* ws, int cap) {
     CubeWs w;
     w.chunks = (4 * n + ITEMS - 1) / ITEMS;
     char* p = (char*)ws;
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        const size_t r = o;
-        o = al(o + bytes);
-        return r;
-    };
-    w.cid = (int32_t*)(p + take(n * 4));
-    w.off = (int32_t*)(p + take(4 * n * 4));
-    w.cse = (uint8_t*)(p + take(n));
-    w.efl = (uint8_t*)(p + take(n));
-    w.csum = (int32_t*)(p + take(w.chunks * 4));
-    w.gtot = (int32_t*)(p + take(4));
-    w.bytes = o;
+    Carve cv;
+    w.cid = (int32_t*)(p + cv.take(n * 4));
+    w.off = (int32_t*)(p + cv.take(4 * n * 4));
+    w.cse = (uint8_t*)(p + cv.take(n));
+    w.efl = (uint8_t*)(p + cv.take(n));
+    w.csum = (int32_t*)(p + cv.take(w.chunks * 4));
+    w.gtot = (int32_t*)(p + cv.take(4));
+    w.bytes = cv.off;
     return w;
-}
-
-__device__ __forceinline__ int64_t gid() { return (int64_t)blockIdx.x * TPB + threadIdx.x; }
-
-// sign code of cube (i,j,k): bit c set when corner c (x-fastest) is inside
-__device__ __forceinline__ unsigned cube_code(const float* __restrict__ s, int res, int i, int j, int k) {
-    const int G = res + 1;
-    unsigned code = 0;
-#pragma unroll
-    for (int c = 0; c < 8; c++) {
-        const size_t gi = ((size_t)(i + (c & 1)) * G + (j + ((c >> 1) & 1))) * G + (k + (c >> 2));
-        code |= (s[gi] < 0.0f ? 1u : 0u) << c;
-    }
-    return code;
 }
 
 __global__ __launch_bounds__(TPB) void k_sf_mark(const float* __restrict__ s, int res, uint64_t* __restrict__ mask, int32_t* __restrict__ bcnt) {
@@ -114,32 +81,13 @@ __global__ __launch_bounds__(TPB) void k_sf_mark(const float* __restrict__ s, in
     const int64_t p = gid(), n = (int64_t)res * res * res;
     bool m = false;
     if (p < n) {
-        const unsigned code = cube_code(s, res, (int)(p / ((int64_t)res * res)), (int)((p / res) % res), (int)(p % res));
+        const unsigned code = flexi_cube_code(s, res, (int)(p / ((int64_t)res * res)), (int)((p / res) % res), (int)(p % res));
         m = code != 0u && code != 255u;
     }
-    const uint64_t w = __ballot(m);  // lanes past n contribute 0: the last word's upper bits are clear
-    if ((threadIdx.x & 63) == 0) {
-        if (p < n) mask[p >> 6] = w;
-        s_w[threadIdx.x >> 6] = __popcll(w);
-    }
+    const uint64_t w = store_word(mask, p, n, m);
+    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = __popcll(w);
     __syncthreads();
     if (threadIdx.x == 0) bcnt[blockIdx.x] = (s_w[0] + s_w[1]) + (s_w[2] + s_w[3]);
-}
-
-// exclusive scan of TPB ints in LDS (Hillis-Steele): this thread's exclusive prefix; *s_tot gets the workgroup's total
-__device__ __forceinline__ int block_exclusive_scan(int v, int* s, int* s_tot) {
-    s[threadIdx.x] = v;
-    __syncthreads();
-    for (int off = 1; off < TPB; off <<= 1) {
-        const int t = (int)threadIdx.x >= off ? s[threadIdx.x - off] : 0;
-        __syncthreads();
-        s[threadIdx.x] += t;
-        __syncthreads();
-    }
-    const int incl = s[threadIdx.x];
-    if (threadIdx.x == TPB - 1) *s_tot = incl;
-    __syncthreads();
-    return incl - v;
 }
 
 // the sequence a scan runs over: the int32 array itself (n_host items, in place), or the 4n items of the surface cubes
@@ -191,7 +139,7 @@ __global__ __launch_bounds__(TPB) void k_sf_scan_chunks(Seq q, int32_t* __restri
     for (int base = 0; base < nb; base += TPB) {
         const int i = base + (int)threadIdx.x;
         const int v = i < nb ? csum[i] : 0;
-        const int ex = block_exclusive_scan(v, s, &tot);
+        const int ex = block_exclusive_scan<TPB>(v, s, &tot);
         if (i < nb) csum[i] = carry + ex;
         carry += tot;
         __syncthreads();  // tot is read before the next round's scan writes it
@@ -216,7 +164,7 @@ __global__ __launch_bounds__(TPB) void k_sf_apply(Seq q, const int32_t* __restri
         v[e] = (base + e < len) ? seq_val(q, base + e, n) : 0;
         sum += v[e];
     }
-    int off = csum[blockIdx.x] + block_exclusive_scan(sum, s, &tot);
+    int off = csum[blockIdx.x] + block_exclusive_scan<TPB>(sum, s, &tot);
 #pragma unroll
     for (int e = 0; e < 8; e++) {
         if (base + e < len) out[base + e] = off;
@@ -248,16 +196,14 @@ __global__ __launch_bounds__(TPB) void k_sf_compact(const uint64_t* __restrict__
         counts[2] = (n < 0 || n > cap) ? FOHO_SFLEXI_OVER_CUBES : 0;
     }
     if (w >= words || n < 0 || n > cap) return;
-    uint64_t m = mask[w];
+    const uint64_t m = mask[w];
     if (!m) return;
     int o = bpre[w >> 2];
     for (int64_t ww = w & ~(int64_t)3; ww < w; ww++) o += __popcll(mask[ww]);
-    while (m) {
-        const int b = __ffsll((unsigned long long)m) - 1;
-        m &= m - 1;
+    for_each_bit(m, [&](int b) {
         if ((unsigned)o < (unsigned)n) cid[o] = (int32_t)(w * 64 + b);  // (a mark buffer of another field cannot write past n)
         o++;
-    }
+    });
 }
 
 __global__ __launch_bounds__(TPB) void k_sf_classify(const float* __restrict__ s, int res, const int32_t* __restrict__ total, int cap,
@@ -269,7 +215,7 @@ __global__ __launch_bounds__(TPB) void k_sf_classify(const float* __restrict__ s
     unsigned code = 0, f = 0;
     if (cube >= 0 && cube < C) {
         const int k = (int)(cube % res), j = (int)((cube / res) % res), i = (int)(cube / ((int64_t)res * res));
-        code = cube_code(s, res, i, j, k);
+        code = flexi_cube_code(s, res, i, j, k);
         // the edge from the minimum corner along an axis ends at a grid point (i, j, k < res); it has four cubes around it when
         // its two transverse coordinates are interior; its ends are corners 0 and 1 / 2 / 4
         const bool ii = i >= 1 && i <= res - 1, jj = j >= 1 && j <= res - 1, kk = k >= 1 && k <= res - 1;
@@ -280,11 +226,6 @@ __global__ __launch_bounds__(TPB) void k_sf_classify(const float* __restrict__ s
     cse[c] = (uint8_t)code;
     efl[c] = (uint8_t)f;
 }
-
-// corner pair of every cube edge (k_flexi.inc: FX_EDGE_TABLES)
-#define SF_EDGE_TABLES                                              \
-    constexpr int fx_ea[12] = {0, 2, 4, 6, 0, 1, 4, 5, 0, 1, 2, 3}; \
-    constexpr int fx_eb[12] = {1, 3, 5, 7, 2, 3, 6, 7, 4, 5, 6, 7};
 
 // flexi_verts_role of k_flexi.inc for compact cube c, the corner positions from the axis tables
 __device__ __forceinline__ void sf_verts_role(int64_t c, int n, const float* __restrict__ axes, const float* __restrict__ s, int res,
@@ -300,7 +241,6 @@ __device__ __forceinline__ void sf_verts_role(int64_t c, int n, const float* __r
         atomicOr(&counts[2], FOHO_SFLEXI_OVER_VERTS);
         return;
     }
-    SF_EDGE_TABLES
     const int G = res + 1;
     const int64_t t = cid[c];
     const int k = (int)(t % res), j = (int)((t / res) % res), i = (int)(t / ((int64_t)res * res));
@@ -313,52 +253,8 @@ __device__ __forceinline__ void sf_verts_role(int64_t c, int n, const float* __r
         xc[3 * q + 1] = axes[G + cj];
         xc[3 * q + 2] = axes[2 * G + ck];
     }
-    for (int p = 0; p < np; p++) {
-        float acc[3] = {0.f, 0.f, 0.f}, cnt = 0.f;
-#pragma unroll
-        for (int e = 0; e < 12; e++) {
-            if (c_flexi_edge_patch[code][e] != p) continue;
-            const int a = fx_ea[e], b = fx_eb[e];
-            const float den = sc[b] - sc[a];
-            for (int q = 0; q < 3; q++) acc[q] += (xc[3 * a + q] * sc[b] - xc[3 * b + q] * sc[a]) / den;
-            cnt += 1.0f;
-        }
-        float v[3];
-        for (int q = 0; q < 3; q++) {
-            v[q] = acc[q] / cnt;
-            verts[3 * (size_t)(base + p) + q] = v[q];
-        }
-        if (ldev) {
-            float dsum = 0.f, dd[12];
-#pragma unroll
-            for (int e = 0; e < 12; e++) {
-                dd[e] = 0.f;
-                if (c_flexi_edge_patch[code][e] != p) continue;
-                const int a = fx_ea[e], b = fx_eb[e];
-                const float den = sc[b] - sc[a];
-                float d2 = 0.f;
-                for (int q = 0; q < 3; q++) {
-                    const float u = (xc[3 * a + q] * sc[b] - xc[3 * b + q] * sc[a]) / den - v[q];
-                    d2 += u * u;
-                }
-                dd[e] = sqrtf(d2);
-                dsum += dd[e];
-            }
-            const float mean = dsum / cnt;
-            float dev = 0.f;
-#pragma unroll
-            for (int e = 0; e < 12; e++)
-                if (c_flexi_edge_patch[code][e] == p) dev += fabsf(dd[e] - mean);
-            ldev[base + p] = dev / cnt;
-        }
-    }
+    for (int p = 0; p < np; p++) flexi_dual_vertex(code, p, sc, xc, verts + 3 * (size_t)(base + p), ldev ? ldev + (base + p) : nullptr);
 }
-
-// the four cubes around an edge (cyclic; the quad's normal points along +axis) and the cube-local id of the edge in each
-// (k_flexi.inc: c_flexi_ring)
-__constant__ signed char c_sf_ring[3][4][4] = {{{0, -1, -1, 3}, {0, 0, -1, 2}, {0, 0, 0, 0}, {0, -1, 0, 1}},
-                                               {{-1, 0, -1, 7}, {-1, 0, 0, 5}, {0, 0, 0, 4}, {0, 0, -1, 6}},
-                                               {{-1, -1, 0, 11}, {0, -1, 0, 10}, {0, 0, 0, 8}, {-1, 0, 0, 9}}};
 
 // flexi_faces_role of k_flexi.inc for item t = axis * n + compact cube: the edge at the cube's minimum corner
 __device__ __forceinline__ void sf_faces_role(int64_t t, int n, int res, const uint64_t* __restrict__ mask, const int32_t* __restrict__ bpre,
@@ -380,25 +276,12 @@ __device__ __forceinline__ void sf_faces_role(int64_t t, int n, int res, const u
 #pragma unroll
     for (int r = 0; r < 4; r++) {
         // the flag says the transverse coordinates are in 1 .. res-1: all four cubes exist, and all contain the sign-changing edge
-        const int ci = i + c_sf_ring[axis][r][0], cj = j + c_sf_ring[axis][r][1], ck = k + c_sf_ring[axis][r][2];
+        const int ci = i + c_flexi_ring[axis][r][0], cj = j + c_flexi_ring[axis][r][1], ck = k + c_flexi_ring[axis][r][2];
         const int rk = rank_of(mask, bpre, ((int64_t)ci * res + cj) * res + ck);
         if ((unsigned)rk >= (unsigned)n) return;  // (a mark buffer of another field)
-        q[r] = (int64_t)off[rk] + c_flexi_edge_patch[cse[rk]][c_sf_ring[axis][r][3]];
+        q[r] = (int64_t)off[rk] + c_flexi_edge_patch[cse[rk]][c_flexi_ring[axis][r][3]];
     }
-    if (!(cse[c] & 1)) {  // orient from the inside end of the edge to the outside end; its near end is corner 0 of this cube
-        const int64_t t0 = q[0], t1 = q[1];
-        q[0] = q[3];
-        q[1] = q[2];
-        q[2] = t1;
-        q[3] = t0;
-    }
-    int64_t* o = faces + 6 * (size_t)qd;
-    o[0] = q[0];
-    o[1] = q[1];
-    o[2] = q[2];
-    o[3] = q[0];
-    o[4] = q[2];
-    o[5] = q[3];
+    flexi_quad(q, cse[c] & 1, faces + 6 * (size_t)qd);  // the edge's near end is corner 0 of this cube
 }
 
 // dual vertices (first nvb workgroups, one surface cube per thread) and quads (the rest, one (axis, surface cube) per thread)
@@ -421,24 +304,14 @@ __global__ __launch_bounds__(TPB) void k_sf_emit(const float* __restrict__ axes,
         sf_faces_role((int64_t)(blockIdx.x - nvb) * TPB + threadIdx.x, n, res, mask, bpre, cid, cse, efl, off, faces, faces_cap, counts);
 }
 
-unsigned blocks_for(size_t n, int per) { return (unsigned)(n ? (n + per - 1) / per : 1); }
-
-int launched(const char* what) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(-2, std::string(what) + ": launch failed: " + hipGetErrorString(e));
-    return 0;
-}
-
 bool res_ok(int32_t r) { return r >= 1 && r <= FOHO_SFLEXI_MAX_RES; }
 bool cap_ok(int32_t c) { return c >= 0 && c <= FOHO_SFLEXI_MAX_CUBES; }
 
 }  // namespace
 
+FOHO_SIDE_ENTRY_POINTS(sflexi, FOHO_SFLEXI_API, FOHO_SFLEXI_VERSION)
+
 extern "C" {
-
-FOHO_SFLEXI_API int foho_sflexi_version(void) { return FOHO_SFLEXI_VERSION; }
-
-FOHO_SFLEXI_API const char* foho_sflexi_last_error(void) { return g_err.c_str(); }
 
 FOHO_SFLEXI_API size_t foho_sflexi_mark_bytes(int32_t res) { return res_ok(res) ? carve_mark(nullptr, res).bytes : 0; }
 

@@ -34,6 +34,7 @@
 #include <string>
 
 #include "../../include/foho_hip.h"
+#include "foho_carve.h"
 #include "foho_common.h"
 
 using namespace foho;
@@ -183,23 +184,18 @@ static inline void raster_blocks(const foho_dims& d, int& rf_h, int& rf_o, int& 
 
 static WS make_ws(const foho_dims& d) {
     WS w;
-    size_t o = 0;
+    Carve cv;
     const size_t P = (size_t)d.H * d.W, R = d.n_renders, B = d.B;
     const size_t V3 = (size_t)d.Vtot * 3 * 4;
     w.btiles_x = (d.W + BTX - 1) / BTX;
     w.nbtiles = w.btiles_x * ((d.H + BTY - 1) / BTY);
-    auto take = [&](size_t bytes) {
-        size_t r = o;
-        o = al(o + bytes);
-        return r;
-    };
     const int G1 = d.grid_res + 1;
     // --- static with the targets (FOHO_STAGE_TARGETS); first, so that their place does not move with the mesh sizes ---
-    w.tile_static = take(B * (size_t)w.nbtiles * 12 * 4);  // loss contributions of the target maps per tile (k_loss.inc)
-    w.image_static = take(B * 12 * 8);                     // ... and per image (double)
+    w.tile_static = cv.take(B * (size_t)w.nbtiles * 12 * 4);  // loss contributions of the target maps per tile (k_loss.inc)
+    w.image_static = cv.take(B * 12 * 8);                     // ... and per image (double)
     // --- zeroed every step (atomic accumulators) ---
-    w.zero_begin = o;
-    w.frac_count = take(R * B * 4);
+    w.zero_begin = cv.off;
+    w.frac_count = cv.take(R * B * 4);
     {
         int rf_h, rf_o, nRh, nRo;
 #ifdef FOHO_NSEG_AUTO
@@ -209,69 +205,69 @@ static WS make_ws(const foho_dims& d) {
 #endif
         w.nseg = nRh + nRo;
     }
-    w.seg_count = take(R * B * (size_t)w.nseg * 4);  // entries in every raster workgroup's segment of the fragment list
-    w.kfix_count = take(R * B * 4);  // pixels whose K = 100 buffer was re-built this step (k_resolve -> frac_bwd_role)
-    w.hit_count = take(R * B * 4);  // tiles with at least one hit pixel, per (render, image)
-    w.bwd_count = take(R * B * 4);  // entries of the backward pass's work list (a dense tile is split into up to 4 entries)
-    w.rstats = take(R * B * sizeof(RStats));
-    w.rslot = take(R * B * NSLOT * sizeof(RSlot));
-    w.g_world = take(V3);
-    w.g_ndc = take(V3);  // dL/d(vertex NDC position), accumulated by k_pix_bwd over all renders
-    w.g_nrm = take(V3);  // dL/d(unit vertex normal) = sum of the colour gradients of the incident faces
-    w.parity = take(B * 2 * (size_t)G1 * G1 * 16);
-    w.int_count = take(B * 4);
-    w.final_ticket = take(B * 4);
-    w.loss_acc = take(R * B * LOSS_SLOTS * NPART * 8);  // 12 loss sums per render x LOSS_SLOTS (double atomics of k_loss, read by k_pix_bwd)
-    w.knn_inv = take(B * (size_t)std::max(d.Vh_max, 1) * 8);  // ~(d2 bits << 32 | index) of the nearest object vertex, atomicMax
-    w.zero_end = o;
+    w.seg_count = cv.take(R * B * (size_t)w.nseg * 4);  // entries in every raster workgroup's segment of the fragment list
+    w.kfix_count = cv.take(R * B * 4);  // pixels whose K = 100 buffer was re-built this step (k_resolve -> frac_bwd_role)
+    w.hit_count = cv.take(R * B * 4);  // tiles with at least one hit pixel, per (render, image)
+    w.bwd_count = cv.take(R * B * 4);  // entries of the backward pass's work list (a dense tile is split into up to 4 entries)
+    w.rstats = cv.take(R * B * sizeof(RStats));
+    w.rslot = cv.take(R * B * NSLOT * sizeof(RSlot));
+    w.g_world = cv.take(V3);
+    w.g_ndc = cv.take(V3);  // dL/d(vertex NDC position), accumulated by k_pix_bwd over all renders
+    w.g_nrm = cv.take(V3);  // dL/d(unit vertex normal) = sum of the colour gradients of the incident faces
+    w.parity = cv.take(B * 2 * (size_t)G1 * G1 * 16);
+    w.int_count = cv.take(B * 4);
+    w.final_ticket = cv.take(B * 4);
+    w.loss_acc = cv.take(R * B * LOSS_SLOTS * NPART * 8);  // 12 loss sums per render x LOSS_SLOTS (double atomics of k_loss, read by k_pix_bwd)
+    w.knn_inv = cv.take(B * (size_t)std::max(d.Vh_max, 1) * 8);  // ~(d2 bits << 32 | index) of the nearest object vertex, atomicMax
+    w.zero_end = cv.off;
     // --- scatter planes of the rasteriser: all-zero outside [k_stage2, k_resolve]; k_resolve puts back to zero what
     // it consumed, FOHO_STAGE_BBOX clears everything (first use / after an aborted step)
-    w.clean_begin = o;
-    w.zkey = take(R * B * P * 8);  // ~(z bits << 32 | face id), atomicMax; 0 = no fragment
-    w.fullb = take(R * B * P);     // 1 = some fragment covers the pixel fully (1 - p == 0): plain byte stores, every writer stores 1
-    w.nfrac = take(R * B * P * 4); // fractional-coverage fragments per pixel (the K = 100 test); only they touch it
-    w.plog = take(R * B * P * 8);  // sum of -log2(1 - p) over the fractional fragments in 2^-40 fixed point (integer atomics:
+    w.clean_begin = cv.off;
+    w.zkey = cv.take(R * B * P * 8);  // ~(z bits << 32 | face id), atomicMax; 0 = no fragment
+    w.fullb = cv.take(R * B * P);     // 1 = some fragment covers the pixel fully (1 - p == 0): plain byte stores, every writer stores 1
+    w.nfrac = cv.take(R * B * P * 4); // fractional-coverage fragments per pixel (the K = 100 test); only they touch it
+    w.plog = cv.take(R * B * P * 8);  // sum of -log2(1 - p) over the fractional fragments in 2^-40 fixed point (integer atomics:
                                    // exact, order independent) -> their product; non-zero <=> the pixel has such a fragment
-    w.tile_touched = take(R * B * (size_t)w.nbtiles);  // 1 = a face's pixel box overlaps the tile this step (raster setup)
-    w.tile_clean = take(R * B * (size_t)w.nbtiles);    // 1 = the tile's p2f entries are known to be all -1
-    w.sim_acc = take(2 * B * (size_t)SIM_ACC * 4);     // deferred update: per step parity, the 36 partial sums of the final stage (float atomics)
-    w.pending = take(B * 4);                           // 1 = a deferred update of image b waits for the next k_xform / finalize
-    w.clean_end = o;
+    w.tile_touched = cv.take(R * B * (size_t)w.nbtiles);  // 1 = a face's pixel box overlaps the tile this step (raster setup)
+    w.tile_clean = cv.take(R * B * (size_t)w.nbtiles);    // 1 = the tile's p2f entries are known to be all -1
+    w.sim_acc = cv.take(2 * B * (size_t)SIM_ACC * 4);     // deferred update: per step parity, the 36 partial sums of the final stage (float atomics)
+    w.pending = cv.take(B * 4);                           // 1 = a deferred update of image b waits for the next k_xform / finalize
+    w.clean_end = cv.off;
     // --- plain scratch ---
-    w.mesh_info = take(B * 2 * sizeof(MeshInfo));
-    w.xf_part = take(B * 2 * VERT_BLOCKS_MAX * 8 * 4);
-    w.vbox = take(B * (size_t)VERT_BLOCKS_MAX * 4 * 8 * 4);  // world-space AABB of every 64 consecutive object vertices (k_xform -> role_knn)
-    w.world = take(V3);
-    w.ndc = take(V3);
-    w.vn_raw = take((size_t)d.Vtot * 16);  // per vertex: normalised raw normal (by the reciprocal) + the reciprocal norm
-    w.vn = take(V3);
-    w.face_ndc = take((size_t)d.Ftot * 9 * 4);
-    w.state_next = take(B * (size_t)STATE_NEXT * 4);   // deferred update: params 16 | adam m 16 | adam v 16 | t | flags, written by k_xform
-    w.pair_v = take((size_t)d.Ftot * 3 * 8);  // per (vertex, incident face) pair, CSR order: the face's 3 vertex ids + the corner (pack_pair)
-    w.p2f = take(R * B * P * 4);
-    w.zbuf = take(R * B * P * 4);
-    w.sdist = take(R * B * P * 4);
-    w.prod = take(R * B * P * 4);
-    w.hit_list = take(R * B * (size_t)w.nbtiles * 4);  // ids of those tiles (k_resolve appends, k_loss walks the list)
-    w.bwd_list = take(R * B * (size_t)w.nbtiles * BWD_SPLIT * 4);  // tile | part << 16 | parts << 20 (k_resolve appends, k_pix_bwd walks it)
-    w.pcol = take(R * B * P * 12);  // colour n_a + n_b + n_c of the hit face (read back by the loss / backward passes)
-    w.frac = take(R * B * (size_t)d.frac_cap * sizeof(FracEntry));  // overflow of the segments (rare)
-    w.frac_seg = take(R * B * (size_t)w.nseg * FRAC_SEG * sizeof(FracEntry));
-    w.act_list = take(R * B * (size_t)w.nbtiles * 4);  // batches: tiles k_resolve has work on this step (k_tile_list), per (render, image)
-    w.act_count = take(R * B * 4);
-    w.kfix = take(R * B * KFIX_MAX * sizeof(KFixEntry));
-    w.loss_part = take(R * B * LOSS_BLOCKS * NPART * 4);
-    w.stats2 = take(R * B * NSTAT * 4);
-    w.g_direct = take(V3);
-    w.knn_idx = take((size_t)d.Vtot * 4);
-    w.knn_d2 = take((size_t)d.Vtot * 4);
-    w.hand_order = take(B * (size_t)std::max(d.Vh_max, 1) * 4);  // lane slot -> hand vertex of the nearest-neighbour role, as a DELTA (all-zero = identity)
-    w.kp3d = take(B * 21 * 3 * 4);
-    w.g_kp3d = take(B * 21 * 3 * 4);
-    w.vert_part = take(B * VERT_BLOCKS_MAX * 8 * 4);
-    w.g_special = take(B * 2 * 6 * 4 * 4);  // moge-space gradient of the 6 arg-min / arg-max vertices of each mesh
-    w.sim_part = take(B * 2 * (size_t)SIM_ROWS_MAX * SIM_NP * 4);
-    w.total = o;
+    w.mesh_info = cv.take(B * 2 * sizeof(MeshInfo));
+    w.xf_part = cv.take(B * 2 * VERT_BLOCKS_MAX * 8 * 4);
+    w.vbox = cv.take(B * (size_t)VERT_BLOCKS_MAX * 4 * 8 * 4);  // world-space AABB of every 64 consecutive object vertices (k_xform -> role_knn)
+    w.world = cv.take(V3);
+    w.ndc = cv.take(V3);
+    w.vn_raw = cv.take((size_t)d.Vtot * 16);  // per vertex: normalised raw normal (by the reciprocal) + the reciprocal norm
+    w.vn = cv.take(V3);
+    w.face_ndc = cv.take((size_t)d.Ftot * 9 * 4);
+    w.state_next = cv.take(B * (size_t)STATE_NEXT * 4);   // deferred update: params 16 | adam m 16 | adam v 16 | t | flags, written by k_xform
+    w.pair_v = cv.take((size_t)d.Ftot * 3 * 8);  // per (vertex, incident face) pair, CSR order: the face's 3 vertex ids + the corner (pack_pair)
+    w.p2f = cv.take(R * B * P * 4);
+    w.zbuf = cv.take(R * B * P * 4);
+    w.sdist = cv.take(R * B * P * 4);
+    w.prod = cv.take(R * B * P * 4);
+    w.hit_list = cv.take(R * B * (size_t)w.nbtiles * 4);  // ids of those tiles (k_resolve appends, k_loss walks the list)
+    w.bwd_list = cv.take(R * B * (size_t)w.nbtiles * BWD_SPLIT * 4);  // tile | part << 16 | parts << 20 (k_resolve appends, k_pix_bwd walks it)
+    w.pcol = cv.take(R * B * P * 12);  // colour n_a + n_b + n_c of the hit face (read back by the loss / backward passes)
+    w.frac = cv.take(R * B * (size_t)d.frac_cap * sizeof(FracEntry));  // overflow of the segments (rare)
+    w.frac_seg = cv.take(R * B * (size_t)w.nseg * FRAC_SEG * sizeof(FracEntry));
+    w.act_list = cv.take(R * B * (size_t)w.nbtiles * 4);  // batches: tiles k_resolve has work on this step (k_tile_list), per (render, image)
+    w.act_count = cv.take(R * B * 4);
+    w.kfix = cv.take(R * B * KFIX_MAX * sizeof(KFixEntry));
+    w.loss_part = cv.take(R * B * LOSS_BLOCKS * NPART * 4);
+    w.stats2 = cv.take(R * B * NSTAT * 4);
+    w.g_direct = cv.take(V3);
+    w.knn_idx = cv.take((size_t)d.Vtot * 4);
+    w.knn_d2 = cv.take((size_t)d.Vtot * 4);
+    w.hand_order = cv.take(B * (size_t)std::max(d.Vh_max, 1) * 4);  // lane slot -> hand vertex of the nearest-neighbour role, as a DELTA (all-zero = identity)
+    w.kp3d = cv.take(B * 21 * 3 * 4);
+    w.g_kp3d = cv.take(B * 21 * 3 * 4);
+    w.vert_part = cv.take(B * VERT_BLOCKS_MAX * 8 * 4);
+    w.g_special = cv.take(B * 2 * 6 * 4 * 4);  // moge-space gradient of the 6 arg-min / arg-max vertices of each mesh
+    w.sim_part = cv.take(B * 2 * (size_t)SIM_ROWS_MAX * SIM_NP * 4);
+    w.total = cv.off;
     return w;
 }
 

@@ -135,28 +135,23 @@ struct VaeLayout {   // scratch of either direction
 };
 static VaeLayout vae_layout(const foho_vae_desc* d) {
     VaeLayout l{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return o;
-    };
+    Carve cv;
     const size_t M = (size_t)d->batch * d->n_tokens, W = d->width, F = d->hidden;
     l.sl = sdpa_layout(d->n_tokens, d->n_tokens, d->heads);
-    l.sdpa = take(l.sl.total);
-    l.stats = take(M * (W / 64) * 8);
-    l.rowstat = take(M * 8);
-    l.h = take(M * F * 2);
-    l.xa = take(M * W * 2);
-    l.xb = take(M * W * 2);
-    l.qkv = take(M * 3 * W * 2);
-    l.o = take(M * W * 2);
-    l.x1 = take(M * W * 2);
-    l.dqkv = take(M * 3 * W * 2);
-    l.dot = take(W * M * 2);        // dO^T of all images (row length M), key-block order of the backward attention's operands
-    l.vtb = take(W * M * 2);        // V^T per image, key-permuted: written by the q | k | v projection's epilogue (EP_PACK), read by the forward attention
-    l.deltab = take(M * (size_t)d->heads * 4);   // written by the epilogue of the GEMM that produces dO (EP_DELTA)
-    l.total = off;
+    l.sdpa = cv.take(l.sl.total);
+    l.stats = cv.take(M * (W / 64) * 8);
+    l.rowstat = cv.take(M * 8);
+    l.h = cv.take(M * F * 2);
+    l.xa = cv.take(M * W * 2);
+    l.xb = cv.take(M * W * 2);
+    l.qkv = cv.take(M * 3 * W * 2);
+    l.o = cv.take(M * W * 2);
+    l.x1 = cv.take(M * W * 2);
+    l.dqkv = cv.take(M * 3 * W * 2);
+    l.dot = cv.take(W * M * 2);        // dO^T of all images (row length M), key-block order of the backward attention's operands
+    l.vtb = cv.take(W * M * 2);        // V^T per image, key-permuted: written by the q | k | v projection's epilogue (EP_PACK), read by the forward attention
+    l.deltab = cv.take(M * (size_t)d->heads * 4);   // written by the epilogue of the GEMM that produces dO (EP_DELTA)
+    l.total = cv.off;
     return l;
 }
 struct VaeSaved {   // what the forward keeps, per layer (offsets inside a layer's record)
@@ -164,29 +159,24 @@ struct VaeSaved {   // what the forward keeps, per layer (offsets inside a layer
 };
 static VaeSaved vae_saved(const foho_vae_desc* d) {
     VaeSaved l{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return o;
-    };
+    Carve cv;
     const size_t M = (size_t)d->batch * d->n_tokens, W = d->width, F = d->hidden;
     bool any_qkn = false;
     for (int i = 0; i < d->n_layers; i++) any_qkn |= d->layers[i].qk_norm != 0;
-    l.x = take(M * W * 2);
-    l.qkv = take(M * 3 * W * 2);
-    l.pre = take(any_qkn ? M * 3 * W * 2 : 0);
-    l.o = take(M * W * 2);
-    l.nlse = take(M * d->heads * 4);
-    l.x1 = take(M * W * 2);
-    l.z = take(M * F * 2);
+    l.x = cv.take(M * W * 2);
+    l.qkv = cv.take(M * 3 * W * 2);
+    l.pre = cv.take(any_qkn ? M * 3 * W * 2 : 0);
+    l.o = cv.take(M * W * 2);
+    l.nlse = cv.take(M * d->heads * 4);
+    l.x1 = cv.take(M * W * 2);
+    l.z = cv.take(M * F * 2);
     // what the backward attention streams besides q | k | v, written by the projection's epilogue (EP_PACK) instead of three row kernels in
     // the backward: the scaled Q rows, their transpose (row length M: all images side by side) and K^T per image, keys in operand order
-    l.qs = take(M * W * 2);
-    l.qst = take(W * M * 2);
-    l.kt = take(W * M * 2);
-    l.per_layer = off;
-    l.total = off * d->n_layers;
+    l.qs = cv.take(M * W * 2);
+    l.qst = cv.take(W * M * 2);
+    l.kt = cv.take(W * M * 2);
+    l.per_layer = cv.off;
+    l.total = cv.off * d->n_layers;
     return l;
 }
 

@@ -6,34 +6,15 @@
 // workgroup, one exclusive scan, then each thread writes the set bits of its word in ascending order -- sorted, repeatable.
 // Compiled with -ffp-contract=off: the midpoint means of foho_vol_fill are plain binary32 sums in a fixed order, which the numpy
 // restatement (tests/vol_ref.py) reproduces bit for bit.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <string>
-
+// The error plumbing, gid, the workgroup scan and the mask-word helpers are foho_side.h's.
+#include "foho_side.h"
 #include "foho_vol.h"
 
 namespace {
 
-thread_local std::string g_err;
-
-int fail(int code, const std::string& msg) {
-    g_err = msg;
-    return code;
-}
-
-constexpr int TPB = 256;
 constexpr int SCAN_TPB = 1024;
 
 __device__ __forceinline__ bool bit_of(const uint64_t* m, int64_t p) { return (m[p >> 6] >> (p & 63)) & 1ull; }
-
-// the wave's predicate bits become word (first point of the wave) / 64; lanes past n contribute 0
-__device__ __forceinline__ void store_word(uint64_t* m, int64_t p, int64_t n, bool pred) {
-    const uint64_t w = __ballot(pred);
-    const int64_t p0 = p - (threadIdx.x & 63);
-    if ((threadIdx.x & 63) == 0 && p0 < n) m[p0 >> 6] = w;
-}
-
-__device__ __forceinline__ int64_t gid() { return (int64_t)blockIdx.x * TPB + threadIdx.x; }
 
 // any set bit of the cell mask (r^3) in the box [i0, i1] x [j0, j1] x [k0, k1] (already clipped)
 __device__ __forceinline__ bool any_in_box(const uint64_t* m, int r, int i0, int i1, int j0, int j1, int k0, int k1) {
@@ -123,36 +104,8 @@ __global__ __launch_bounds__(TPB) void k_vol_close_select(const uint64_t* __rest
             s = all || any_in_box(near, R, max(I - 1, 0), min(I, R - 1), max(J - 1, 0), min(J, R - 1), max(K - 1, 0), min(K, R - 1));
         }
     }
-    const uint64_t w = __ballot(s);
-    const int64_t p0 = p - (threadIdx.x & 63);
-    if ((threadIdx.x & 63) == 0 && p0 < n) {
-        sel[p0 >> 6] = w;
-        dec[p0 >> 6] = old | w;
-    }
-}
-
-__device__ __forceinline__ int word_bits(const uint64_t* m, int64_t w, int64_t n_points) {
-    const int64_t left = n_points - w * 64;
-    if (left <= 0) return 0;
-    const uint64_t v = left >= 64 ? m[w] : (m[w] & ((1ull << left) - 1));
-    return __popcll(v);
-}
-
-// exclusive scan of TPB ints in LDS (Hillis-Steele), returns this thread's exclusive prefix; s_tot gets the block total
-template <int N>
-__device__ __forceinline__ int block_exclusive_scan(int v, int* s, int* s_tot) {
-    s[threadIdx.x] = v;
-    __syncthreads();
-    for (int off = 1; off < N; off <<= 1) {
-        const int t = threadIdx.x >= off ? s[threadIdx.x - off] : 0;
-        __syncthreads();
-        s[threadIdx.x] += t;
-        __syncthreads();
-    }
-    const int incl = s[threadIdx.x];
-    if (threadIdx.x == N - 1) *s_tot = incl;
-    __syncthreads();
-    return incl - v;
+    const uint64_t w = store_word(sel, p, n, s);
+    if ((threadIdx.x & 63) == 0 && p < n) dec[p >> 6] = old | w;
 }
 
 // one mask word per thread
@@ -160,7 +113,7 @@ __global__ __launch_bounds__(TPB) void k_vol_count(const uint64_t* __restrict__ 
     __shared__ int s[TPB];
     __shared__ int tot;
     const int64_t w = gid();
-    block_exclusive_scan<TPB>(word_bits(sel, w, n_points), s, &tot);
+    block_exclusive_scan<TPB, int>(__popcll(clipped_word(sel, w, n_points)), s, &tot);
     if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
 }
 
@@ -186,15 +139,10 @@ __global__ __launch_bounds__(TPB) void k_vol_emit(const uint64_t* __restrict__ s
     __shared__ int s[TPB];
     __shared__ int tot;
     const int64_t G = r + 1, n_points = G * G * G, w = gid();
-    const int c = word_bits(sel, w, n_points);
-    int o = boff[blockIdx.x] + block_exclusive_scan<TPB>(c, s, &tot);
-    if (c == 0) return;
-    const int64_t left = n_points - w * 64;
-    uint64_t m = left >= 64 ? sel[w] : (sel[w] & ((1ull << left) - 1));
+    const uint64_t m = clipped_word(sel, w, n_points);
+    int o = boff[blockIdx.x] + block_exclusive_scan<TPB, int>(__popcll(m), s, &tot);
     const int64_t T = R + 1;
-    while (m) {
-        const int b = __ffsll((unsigned long long)m) - 1;
-        m &= m - 1;
+    for_each_bit(m, [&](int b) {
         const int64_t p = w * 64 + b;
         const int k = (int)(p % G), j = (int)((p / G) % G), i = (int)(p / (G * G));
         idx[o] = (int32_t)p;
@@ -202,7 +150,7 @@ __global__ __launch_bounds__(TPB) void k_vol_emit(const uint64_t* __restrict__ s
         xyz[3 * (int64_t)o + 1] = tab[T + (int64_t)j * stride];
         xyz[3 * (int64_t)o + 2] = tab[2 * T + (int64_t)k * stride];
         o++;
-    }
+    });
 }
 
 // value at even indices, else the mean of the 2 / 4 / 8 enclosing coarse corners, summed x-corner outermost, z innermost
@@ -229,23 +177,13 @@ __global__ __launch_bounds__(TPB) void k_vol_scatter(const int32_t* __restrict__
     if (q < n) f[idx[q]] = v[q];
 }
 
-unsigned blocks_for(int64_t n) { return (unsigned)((n + TPB - 1) / TPB); }
-
-int launched(const char* what) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(-2, std::string(what) + ": launch failed: " + hipGetErrorString(e));
-    return 0;
-}
-
 bool res_ok(int32_t r) { return r >= 1 && r <= FOHO_VOL_MAX_RES; }
 
 }  // namespace
 
+FOHO_SIDE_ENTRY_POINTS(vol, FOHO_VOL_API, FOHO_VOL_VERSION)
+
 extern "C" {
-
-FOHO_VOL_API int foho_vol_version(void) { return FOHO_VOL_VERSION; }
-
-FOHO_VOL_API const char* foho_vol_last_error(void) { return g_err.c_str(); }
 
 FOHO_VOL_API int foho_vol_mark(const float* field, int32_t r, int32_t band, uint64_t* mixed, uint64_t* active, void* stream) {
     if (!field || !mixed || !active) return fail(-1, "foho_vol_mark: null argument");

@@ -14,13 +14,9 @@
 //
 // Grid point (i,j,k) -> (i*G + j)*G + k (generate_dense_grid_points, PL:341-360); cube corners in x-fastest order; cube edges
 // 0-3 along x, 4-7 along y, 8-11 along z (followmyhold_amd/flexi_tables.py).
-#include "k_flexi_tables.inc"
-
-// corner pair of every cube edge; constexpr so that the unrolled loops index the corner registers statically (a
-// run-time index would push the 8 + 24 corner values into scratch memory)
-#define FX_EDGE_TABLES                                                         \
-    constexpr int fx_ea[12] = {0, 2, 4, 6, 0, 1, 4, 5, 0, 1, 2, 3};            \
-    constexpr int fx_eb[12] = {1, 3, 5, 7, 2, 3, 6, 7, 4, 5, 6, 7};
+// The per-cube arithmetic (sign code, dual vertex and l_dev, ring table, quad orientation and split) is flexi_core.h's, shared with the
+// sparse extractor (foho_sflexi.hip).
+#include "flexi_core.h"
 
 constexpr int FX_ITEMS = 2048;  // items per workgroup of the scan (256 threads x 8)
 
@@ -33,21 +29,16 @@ static FlexiWs carve_flexi(void* ws, int res) {
     const size_t G = (size_t)res + 1, C = (size_t)res * res * res, E = 3 * G * G * G;
     const size_t nbv = (C + FX_ITEMS - 1) / FX_ITEMS, nbf = (E + FX_ITEMS - 1) / FX_ITEMS;
     char* p = (char*)ws;
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        size_t r = o;
-        o = al(o + bytes);
-        return r;
-    };
+    Carve cv;
     FlexiWs w;
-    w.cse = (uint8_t*)(p + take(C));
-    w.npatch = (int32_t*)(p + take(C * 4));
-    w.v_off = (int32_t*)(p + take(C * 4));
-    w.ecross = (int32_t*)(p + take(E * 4));
-    w.f_off = (int32_t*)(p + take(E * 4));
-    w.bsum_v = (int32_t*)(p + take((nbv + 1) * 4));
-    w.bsum_f = (int32_t*)(p + take((nbf + 1) * 4));
-    w.total = o;
+    w.cse = (uint8_t*)(p + cv.take(C));
+    w.npatch = (int32_t*)(p + cv.take(C * 4));
+    w.v_off = (int32_t*)(p + cv.take(C * 4));
+    w.ecross = (int32_t*)(p + cv.take(E * 4));
+    w.f_off = (int32_t*)(p + cv.take(E * 4));
+    w.bsum_v = (int32_t*)(p + cv.take((nbv + 1) * 4));
+    w.bsum_f = (int32_t*)(p + cv.take((nbf + 1) * 4));
+    w.total = cv.off;
     return w;
 }
 
@@ -62,12 +53,7 @@ __global__ __launch_bounds__(256) void k_flexi_classify(const float* s, int res,
     const size_t C = (size_t)res * res * res, G3 = (size_t)G * G * G;
     if (t < C) {
         const int k = (int)(t % res), j = (int)((t / res) % res), i = (int)(t / ((size_t)res * res));
-        unsigned code = 0;
-#pragma unroll
-        for (int c = 0; c < 8; c++) {
-            const size_t gi = ((size_t)(i + (c & 1)) * G + (j + ((c >> 1) & 1))) * G + (k + (c >> 2));
-            code |= (s[gi] < 0.0f ? 1u : 0u) << c;
-        }
+        const unsigned code = flexi_cube_code(s, res, i, j, k);
         cse[t] = (uint8_t)code;
         npatch[t] = c_flexi_npatch[code];
     }
@@ -263,56 +249,11 @@ __device__ __forceinline__ void flexi_verts_role(size_t t, const float* x, const
         atomicOr(&counts[2], 1);
         return;
     }
-    FX_EDGE_TABLES
     const unsigned code = cse[t];
     float sc[8], xc[24];
     flexi_corners(x, s, res, t, sc, xc);
-    for (int p = 0; p < np; p++) {
-        float acc[3] = {0.f, 0.f, 0.f}, cnt = 0.f;
-#pragma unroll
-        for (int e = 0; e < 12; e++) {
-            if (c_flexi_edge_patch[code][e] != p) continue;
-            const int a = fx_ea[e], b = fx_eb[e];
-            const float den = sc[b] - sc[a];
-            for (int q = 0; q < 3; q++) acc[q] += (xc[3 * a + q] * sc[b] - xc[3 * b + q] * sc[a]) / den;
-            cnt += 1.0f;
-        }
-        float v[3];
-        for (int q = 0; q < 3; q++) {
-            v[q] = acc[q] / cnt;
-            verts[3 * (size_t)(base + p) + q] = v[q];
-        }
-        if (ldev) {
-            float dsum = 0.f, dd[12];
-#pragma unroll
-            for (int e = 0; e < 12; e++) {
-                dd[e] = 0.f;
-                if (c_flexi_edge_patch[code][e] != p) continue;
-                const int a = fx_ea[e], b = fx_eb[e];
-                const float den = sc[b] - sc[a];
-                float d2 = 0.f;
-                for (int q = 0; q < 3; q++) {
-                    const float u = (xc[3 * a + q] * sc[b] - xc[3 * b + q] * sc[a]) / den - v[q];
-                    d2 += u * u;
-                }
-                dd[e] = sqrtf(d2);
-                dsum += dd[e];
-            }
-            const float mean = dsum / cnt;
-            float dev = 0.f;
-#pragma unroll
-            for (int e = 0; e < 12; e++)
-                if (c_flexi_edge_patch[code][e] == p) dev += fabsf(dd[e] - mean);
-            ldev[base + p] = dev / cnt;
-        }
-    }
+    for (int p = 0; p < np; p++) flexi_dual_vertex(code, p, sc, xc, verts + 3 * (size_t)(base + p), ldev ? ldev + (base + p) : nullptr);
 }
-
-// the four cubes around an edge (cyclic; the quad's normal points along +axis) and the cube-local id of the edge in each
-__constant__ signed char c_flexi_ring[3][4][4] = {
-    {{0, -1, -1, 3}, {0, 0, -1, 2}, {0, 0, 0, 0}, {0, -1, 0, 1}},
-    {{-1, 0, -1, 7}, {-1, 0, 0, 5}, {0, 0, 0, 4}, {0, 0, -1, 6}},
-    {{-1, -1, 0, 11}, {0, -1, 0, 10}, {0, 0, 0, 8}, {-1, 0, 0, 9}}};
 
 __device__ __forceinline__ void flexi_faces_role(size_t t, const float* s, int res, const uint8_t* cse, const int32_t* v_off,
                                                  const int32_t* ecross, const int32_t* f_off, int64_t* faces, int cap, int32_t* counts) {
@@ -334,20 +275,7 @@ __device__ __forceinline__ void flexi_faces_role(size_t t, const float* s, int r
         const size_t cid = ((size_t)ci * res + cj) * res + ck;
         q[c] = (int64_t)v_off[cid] + c_flexi_edge_patch[cse[cid]][c_flexi_ring[axis][c][3]];
     }
-    if (!(s[r] < 0.0f)) {  // orient from the inside end of the edge to the outside end
-        const int64_t t0 = q[0], t1 = q[1];
-        q[0] = q[3];
-        q[1] = q[2];
-        q[2] = t1;
-        q[3] = t0;
-    }
-    int64_t* o = faces + 6 * (size_t)qd;
-    o[0] = q[0];
-    o[1] = q[1];
-    o[2] = q[2];
-    o[3] = q[0];
-    o[4] = q[2];
-    o[5] = q[3];
+    flexi_quad(q, s[r] < 0.0f, faces + 6 * (size_t)qd);  // the edge's near end is grid point r
 }
 
 // dual vertices (first nvb workgroups, one cube per thread) and quads (the rest, one grid edge per thread) in one launch
@@ -406,7 +334,7 @@ __global__ __launch_bounds__(256) void k_flexi_bwd(const float* x, const float* 
     if (base + np > n_verts) return;
     const int G = res + 1;
     const int k = (int)(t % res), j = (int)((t / res) % res), i = (int)(t / ((size_t)res * res));
-    FX_EDGE_TABLES
+    FLEXI_EDGE_TABLES
     const unsigned code = cse[t];
     float sc[8], xc[24];
     flexi_corners(x, s, res, t, sc, xc);

@@ -151,17 +151,12 @@ class HipGeoDecoder:
         for fn in (self.lib.foho_geo_workspace_bytes, self.lib.foho_geo_bwd_workspace_bytes):
             fn.restype = ctypes.c_size_t
             fn.argtypes = [ctypes.POINTER(FohoGeoWeights), ctypes.c_int32]
-        self.lib.foho_geo_last_error.restype = ctypes.c_char_p
         if self.lib.foho_geo_workspace_bytes(ctypes.byref(w), self.chunk) == 0:
-            raise L.FohoError(f"HipGeoDecoder: {self.lib.foho_geo_last_error().decode()}")
+            raise L.FohoError(f"HipGeoDecoder: {L.geo_error()}")
 
     @classmethod
     def from_module(cls, module, device="cuda", chunk_rows=None):
         return cls(_parts(module), device=device, chunk_rows=chunk_rows)
-
-    def _check(self, status, what):
-        if status != 0:
-            raise L.FohoError(f"{what} failed ({status}): {self.lib.foho_geo_last_error().decode()}")
 
     def prepare(self, latents):
         """LayerNorm + K/V projection of the latent tokens (L, width), once per set of tokens."""
@@ -170,7 +165,7 @@ class HipGeoDecoder:
             raise L.FohoError(f"HipGeoDecoder: latent tokens of width {lat.shape[1]}, decoder of width {self.w.width}")
         self._size_for(lat.shape[0])
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        self._check(self.lib.foho_geo_prepare(ctypes.byref(self.w), L.vp(lat.data_ptr()), ctypes.c_int32(self.chunk), L.vp(self.workspace.data_ptr()),
+        L.geo_check(self.lib.foho_geo_prepare(ctypes.byref(self.w), L.vp(lat.data_ptr()), ctypes.c_int32(self.chunk), L.vp(self.workspace.data_ptr()),
                                               ctypes.c_size_t(self.workspace.numel()), L.vp(stream)), "foho_geo_prepare")
         self._lat = lat        # kept alive until the stream has consumed it
         self._ws_epoch += 1
@@ -180,7 +175,7 @@ class HipGeoDecoder:
             self.w.n_latents = n_latents
             n = int(self.lib.foho_geo_workspace_bytes(ctypes.byref(self.w), self.chunk))
             if n == 0:
-                raise L.FohoError(f"HipGeoDecoder: {self.lib.foho_geo_last_error().decode()}")
+                raise L.FohoError(f"HipGeoDecoder: {L.geo_error()}")
             self.workspace = torch.empty(n, dtype=torch.uint8, device=self.device)
             self.bwd_workspace = None
             self._ws_epoch += 1
@@ -205,7 +200,7 @@ class HipGeoDecoder:
             raise L.FohoError(f"HipGeoDecoder: kv of shape {tuple(kv.shape)}, decoder of width {self.w.width}")
         self._size_for(kv.shape[0])
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        self._check(self.lib.foho_geo_set_kv(ctypes.byref(self.w), L.vp(kv.data_ptr()), ctypes.c_int32(self.chunk), L.vp(self.workspace.data_ptr()),
+        L.geo_check(self.lib.foho_geo_set_kv(ctypes.byref(self.w), L.vp(kv.data_ptr()), ctypes.c_int32(self.chunk), L.vp(self.workspace.data_ptr()),
                                              ctypes.c_size_t(self.workspace.numel()), L.vp(stream)), "foho_geo_set_kv")
         self._prepared = None
         self._ws_epoch += 1
@@ -244,7 +239,7 @@ class HipGeoDecoder:
         out = torch.empty(q.shape[0], dtype=torch.float32, device=self.device)
         bws = self._bwd_ws()
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        self._check(self.lib.foho_geo_decode_fwd_keep(ctypes.byref(self.w), L.vp(q.data_ptr()), ctypes.c_int64(q.shape[0]), L.vp(out.data_ptr()),
+        L.geo_check(self.lib.foho_geo_decode_fwd_keep(ctypes.byref(self.w), L.vp(q.data_ptr()), ctypes.c_int64(q.shape[0]), L.vp(out.data_ptr()),
                                                       ctypes.c_int32(self.chunk), L.vp(self.workspace.data_ptr()), ctypes.c_size_t(self.workspace.numel()),
                                                       L.vp(bws.data_ptr()), ctypes.c_size_t(bws.numel()), L.vp(saved.data_ptr()),
                                                       ctypes.c_size_t(saved.numel()), L.vp(stream)), "foho_geo_decode_fwd_keep")
@@ -260,7 +255,7 @@ class HipGeoDecoder:
         bws = self._bwd_ws()
         out = torch.empty(self.w.n_latents, 2 * self.w.width, dtype=torch.float32, device=self.device)
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        self._check(self.lib.foho_geo_decode_bwd(ctypes.byref(self.w), L.vp(q.data_ptr()), ctypes.c_int64(q.shape[0]), L.vp(g.data_ptr()),
+        L.geo_check(self.lib.foho_geo_decode_bwd(ctypes.byref(self.w), L.vp(q.data_ptr()), ctypes.c_int64(q.shape[0]), L.vp(g.data_ptr()),
                                                  L.vp(out.data_ptr()), ctypes.c_int32(self.chunk), L.vp(self.workspace.data_ptr()),
                                                  ctypes.c_size_t(self.workspace.numel()), L.vp(bws.data_ptr()), ctypes.c_size_t(bws.numel()),
                                                  L.vp(saved.data_ptr()) if saved is not None else None,
@@ -286,7 +281,7 @@ class HipGeoDecoder:
         out = torch.empty(self.w.n_latents, 2 * self.w.width, dtype=torch.float32, device=self.device)
         stats = torch.zeros(2, dtype=torch.int32, device=self.device)
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        self._check(self.lib.foho_geo_decode_bwd_rows(ctypes.byref(self.w), L.vp(q.data_ptr()), ctypes.c_int64(n), L.vp(g.data_ptr()), L.vp(out.data_ptr()),
+        L.geo_check(self.lib.foho_geo_decode_bwd_rows(ctypes.byref(self.w), L.vp(q.data_ptr()), ctypes.c_int64(n), L.vp(g.data_ptr()), L.vp(out.data_ptr()),
                                                       ctypes.c_int64(cap), ctypes.c_int32(self.chunk), L.vp(self.workspace.data_ptr()),
                                                       ctypes.c_size_t(self.workspace.numel()), L.vp(bws.data_ptr()), ctypes.c_size_t(bws.numel()),
                                                       L.vp(self._rows_ws.data_ptr()), ctypes.c_size_t(self._rows_ws.numel()), L.vp(stats.data_ptr()),
@@ -318,7 +313,7 @@ class HipGeoDecoder:
         need = int(self.lib.foho_geo_query_cache_bytes(ctypes.byref(self.w), ctypes.c_int64(q.shape[0])))
         buf = torch.empty(need, dtype=torch.uint8, device=self.device)
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        self._check(self.lib.foho_geo_prepare_queries(ctypes.byref(self.w), L.vp(q.data_ptr()), ctypes.c_int64(q.shape[0]), ctypes.c_int32(self.chunk),
+        L.geo_check(self.lib.foho_geo_prepare_queries(ctypes.byref(self.w), L.vp(q.data_ptr()), ctypes.c_int64(q.shape[0]), ctypes.c_int32(self.chunk),
                                                       L.vp(self.workspace.data_ptr()), ctypes.c_size_t(self.workspace.numel()), L.vp(buf.data_ptr()),
                                                       ctypes.c_size_t(need), L.vp(stream)), "foho_geo_prepare_queries")
         # keyed by storage address + version + size, with the tensor kept alive (so the address cannot be handed to another one)
@@ -360,12 +355,12 @@ class HipGeoDecoder:
         out = torch.empty(q.shape[0], dtype=torch.float32, device=self.device)
         stream = torch.cuda.current_stream(self.device).cuda_stream
         if cache is not None:
-            self._check(self.lib.foho_geo_decode_fwd_cached(ctypes.byref(self.w), L.vp(q.data_ptr()), ctypes.c_int64(q.shape[0]), L.vp(cache.data_ptr()),
+            L.geo_check(self.lib.foho_geo_decode_fwd_cached(ctypes.byref(self.w), L.vp(q.data_ptr()), ctypes.c_int64(q.shape[0]), L.vp(cache.data_ptr()),
                                                             ctypes.c_size_t(cache.numel()), L.vp(out.data_ptr()), ctypes.c_int32(self.chunk),
                                                             L.vp(self.workspace.data_ptr()), ctypes.c_size_t(self.workspace.numel()), L.vp(stream)),
                         "foho_geo_decode_fwd_cached")
             return out
-        self._check(self.lib.foho_geo_decode_fwd(ctypes.byref(self.w), L.vp(q.data_ptr()), ctypes.c_int64(q.shape[0]), L.vp(out.data_ptr()),
+        L.geo_check(self.lib.foho_geo_decode_fwd(ctypes.byref(self.w), L.vp(q.data_ptr()), ctypes.c_int64(q.shape[0]), L.vp(out.data_ptr()),
                                                  ctypes.c_int32(self.chunk), L.vp(self.workspace.data_ptr()), ctypes.c_size_t(self.workspace.numel()),
                                                  L.vp(stream)), "foho_geo_decode_fwd")
         return out

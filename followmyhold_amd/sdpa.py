@@ -62,10 +62,6 @@ def _desc(q, k):
     return FohoSdpaDesc(M, k.shape[2], H, B, q.stride(0), q.stride(2), q.stride(1), k.stride(0), k.stride(2), k.stride(1))
 
 
-def _stream(t):
-    return L.vp(torch.cuda.current_stream(t.device).cuda_stream)
-
-
 # Which backward follows the HIP forward.  "hip" (default): foho_sdpa_bwd -- k_geo_attn_bwd (dK / dV written directly, one workgroup per
 # (head, key block)) + k_geo_attn_dq: this package's own kernels, bitwise repeatable.  "torch" (opt-in, FOHO_VAE_SDPA=hip_torch_bwd): torch's
 # memory-efficient attention backward fed with this forward's output and log-sum-exp -- a PRIVATE operator
@@ -99,10 +95,8 @@ class _HipSdpaFn(torch.autograd.Function):
         ws = _workspace(lib, q.device, M, Lk, H)
         d = _desc(q, k)
         rc = lib.foho_sdpa_fwd(ctypes.byref(d), L.vp(q.data_ptr()), L.vp(k.data_ptr()), L.vp(v.data_ptr()), L.vp(out.data_ptr()), L.vp(nlse.data_ptr()),
-                               L.vp(lse.data_ptr()) if lse is not None else None, L.vp(ws.data_ptr()), ctypes.c_size_t(ws.numel()), _stream(q))
-        if rc != 0:
-            lib.foho_geo_last_error.restype = ctypes.c_char_p
-            raise L.FohoError(f"foho_sdpa_fwd failed ({rc}): {lib.foho_geo_last_error().decode()}")
+                               L.vp(lse.data_ptr()) if lse is not None else None, L.vp(ws.data_ptr()), ctypes.c_size_t(ws.numel()), L._stream(q.device))
+        L.geo_check(rc, "foho_sdpa_fwd")
         if lse is not None:
             ctx.save_for_backward(q, k, v, out, nlse, lse)
         else:
@@ -138,10 +132,8 @@ class _HipSdpaFn(torch.autograd.Function):
         d = _desc(q, k)
         rc = lib.foho_sdpa_bwd(ctypes.byref(d), L.vp(q.data_ptr()), L.vp(k.data_ptr()), L.vp(v.data_ptr()), L.vp(out.data_ptr()), L.vp(nlse.data_ptr()),
                                L.vp(go.data_ptr()), L.vp(gq.data_ptr()), L.vp(gk.data_ptr()), L.vp(gv.data_ptr()), L.vp(ws.data_ptr()),
-                               ctypes.c_size_t(ws.numel()), _stream(g))
-        if rc != 0:
-            lib.foho_geo_last_error.restype = ctypes.c_char_p
-            raise L.FohoError(f"foho_sdpa_bwd failed ({rc}): {lib.foho_geo_last_error().decode()}")
+                               ctypes.c_size_t(ws.numel()), L._stream(g.device))
+        L.geo_check(rc, "foho_sdpa_bwd")
         return gq.view(B, M, H, 64).transpose(1, 2), gk.view(B, Lk, H, 64).transpose(1, 2), gv.view(B, Lk, H, 64).transpose(1, 2)
 
 

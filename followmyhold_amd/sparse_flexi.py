@@ -15,50 +15,31 @@ The kernels are libfoho_sflexi.so's (csrc/foho_sflexi.hip, C ABI csrc/foho_sflex
 when the library is missing or of another version.
 """
 import ctypes
-import os
 
 import numpy as np
 import torch
 
-from ._lib import FohoError, vp
+from . import _lib as L_
+from ._lib import FohoError, _p, _stream, vp
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-SO_PATH = os.path.join(_HERE, "libfoho_sflexi.so")
-VERSION = 100           # FOHO_SFLEXI_VERSION of csrc/foho_sflexi.h
+SO_PATH = L_.side_path("sflexi")
+VERSION = L_.SIDE_VERSIONS["sflexi"]      # FOHO_SFLEXI_VERSION of csrc/foho_sflexi.h
 MAX_RES = 1024          # FOHO_SFLEXI_MAX_RES
 MAX_CUBES = 1 << 26     # FOHO_SFLEXI_MAX_CUBES
 OVER_VERTS, OVER_FACES, OVER_CUBES = 1, 2, 4
-_lib = None
+_i32, _sz, _rc = ctypes.c_int32, ctypes.c_size_t, ctypes.c_int
+_SIGNATURES = {
+    "foho_sflexi_mark_bytes": (_sz, [_i32]), "foho_sflexi_cube_bytes": (_sz, [_i32]), "foho_sflexi_workspace_bytes": (_sz, [_i32, _i32]),
+    "foho_sflexi_mark": (_rc, [vp, _i32, vp, _sz, vp, vp]),
+    "foho_sflexi_extract": (_rc, [vp, vp, _i32, vp, _sz, _i32, vp, _i32, vp, _i32, vp, vp, vp, _sz, vp])}
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(SO_PATH):
-            raise FohoError(f"{SO_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` (there is no CPU fallback)")
-        L = ctypes.CDLL(SO_PATH)
-        L.foho_sflexi_version.restype = ctypes.c_int
-        if L.foho_sflexi_version() != VERSION:
-            raise FohoError(f"{SO_PATH} is version {L.foho_sflexi_version()}, this binding is {VERSION}: rebuild (make -C followmyhold_amd/csrc)")
-        L.foho_sflexi_last_error.restype = ctypes.c_char_p
-        i32, sz = ctypes.c_int32, ctypes.c_size_t
-        L.foho_sflexi_mark_bytes.restype, L.foho_sflexi_mark_bytes.argtypes = sz, [i32]
-        L.foho_sflexi_cube_bytes.restype, L.foho_sflexi_cube_bytes.argtypes = sz, [i32]
-        L.foho_sflexi_workspace_bytes.restype, L.foho_sflexi_workspace_bytes.argtypes = sz, [i32, i32]
-        L.foho_sflexi_mark.restype, L.foho_sflexi_mark.argtypes = ctypes.c_int, [vp, i32, vp, sz, vp, vp]
-        L.foho_sflexi_extract.restype = ctypes.c_int
-        L.foho_sflexi_extract.argtypes = [vp, vp, i32, vp, sz, i32, vp, i32, vp, i32, vp, vp, vp, sz, vp]
-        _lib = L
-    return _lib
+    return L_.load_side("sflexi", _SIGNATURES)
 
 
 def _check(status, what):
-    if status != 0:
-        raise FohoError(f"{what} failed ({status}): {lib().foho_sflexi_last_error().decode()}")
-
-
-def _p(t):
-    return None if t is None else vp(t.data_ptr())
+    L_.check_side(lib(), "foho_sflexi", status, what)
 
 
 def grid_axes(bbox_min, bbox_max, res):
@@ -86,7 +67,7 @@ def flexicubes_sparse(axes, s, res, return_stats=False):
     if ax.shape != (3, G) or ss.numel() != G ** 3:
         raise FohoError(f"flexicubes_sparse: expected {(3, G)} axis tables and {G ** 3} SDF values")
     L = lib()
-    st = vp(torch.cuda.current_stream(dev).cuda_stream)
+    st = _stream(dev)
     n_marks = L.foho_sflexi_mark_bytes(res)
     marks = torch.empty(n_marks, dtype=torch.uint8, device=dev)
     n_dev = torch.empty(1, dtype=torch.int32, device=dev)

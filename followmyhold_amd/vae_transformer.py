@@ -145,12 +145,11 @@ class HipVaeTransformer:
         for fn in (self.lib.foho_vae_workspace_bytes, self.lib.foho_vae_saved_bytes):
             fn.restype = ctypes.c_size_t
             fn.argtypes = [ctypes.POINTER(FohoVaeDesc)]
-        self.lib.foho_geo_last_error.restype = ctypes.c_char_p
         self.flags = 0                    # foho_vae_desc.flags (A/B switches; 0 = the product path)
         self.calls = 0                    # forwards served (pipeline diagnostics: was the HIP route taken?)
         d = self._desc(1, 128)
         if int(self.lib.foho_vae_workspace_bytes(ctypes.byref(d))) == 0:
-            raise L.FohoError(f"HipVaeTransformer: {self.lib.foho_geo_last_error().decode()}")
+            raise L.FohoError(f"HipVaeTransformer: {L.geo_error()}")
 
     @classmethod
     def from_module(cls, vae, device="cuda"):
@@ -177,15 +176,11 @@ class HipVaeTransformer:
         if ws is None:
             n = int(self.lib.foho_vae_workspace_bytes(ctypes.byref(d)))
             if n == 0:
-                raise L.FohoError(f"HipVaeTransformer: {self.lib.foho_geo_last_error().decode()}")
+                raise L.FohoError(f"HipVaeTransformer: {L.geo_error()}")
             if len(self._ws) >= 2:
                 self._ws.clear()
             ws = self._ws[key] = torch.empty(n, dtype=torch.uint8, device=self.device)
         return ws
-
-    def _check(self, rc, what):
-        if rc != 0:
-            raise L.FohoError(f"{what} failed ({rc}): {self.lib.foho_geo_last_error().decode()}")
 
     def forward_raw(self, x, keep):
         """-> (out (B, L, width) fp16, saved or None)"""
@@ -199,7 +194,7 @@ class HipVaeTransformer:
             saved = torch.empty(int(self.lib.foho_vae_saved_bytes(ctypes.byref(d))), dtype=torch.uint8, device=self.device)
         out = torch.empty_like(x)
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        self._check(self.lib.foho_vae_fwd(ctypes.byref(d), L.vp(x.data_ptr()), L.vp(out.data_ptr()), L.vp(ws.data_ptr()), ctypes.c_size_t(ws.numel()),
+        L.geo_check(self.lib.foho_vae_fwd(ctypes.byref(d), L.vp(x.data_ptr()), L.vp(out.data_ptr()), L.vp(ws.data_ptr()), ctypes.c_size_t(ws.numel()),
                                           L.vp(saved.data_ptr()) if saved is not None else None, ctypes.c_size_t(saved.numel() if saved is not None else 0),
                                           L.vp(stream)), "foho_vae_fwd")
         self.calls += 1
@@ -211,7 +206,7 @@ class HipVaeTransformer:
         ws = self._workspace(d)
         gx = torch.empty(shape, dtype=torch.float16, device=self.device)
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        self._check(self.lib.foho_vae_bwd(ctypes.byref(d), L.vp(g.data_ptr()), L.vp(gx.data_ptr()), L.vp(ws.data_ptr()), ctypes.c_size_t(ws.numel()),
+        L.geo_check(self.lib.foho_vae_bwd(ctypes.byref(d), L.vp(g.data_ptr()), L.vp(gx.data_ptr()), L.vp(ws.data_ptr()), ctypes.c_size_t(ws.numel()),
                                           L.vp(saved.data_ptr()), ctypes.c_size_t(saved.numel()), L.vp(stream)), "foho_vae_bwd")
         return gx
 

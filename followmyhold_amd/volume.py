@@ -23,54 +23,30 @@ images in lockstep through hierarchical_grid_logits_batch.
 There is no CPU path: the binding raises when the library is missing or of another version.
 """
 import ctypes
-import os
 
 import numpy as np
 import torch
 
-from ._lib import FohoError, vp
+from . import _lib as L_
+from ._lib import FohoError, _p, _stream, vp
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-SO_PATH = os.path.join(_HERE, "libfoho_vol.so")
-VERSION = 100           # FOHO_VOL_VERSION of csrc/foho_vol.h
+SO_PATH = L_.side_path("vol")
+VERSION = L_.SIDE_VERSIONS["vol"]      # FOHO_VOL_VERSION of csrc/foho_vol.h
 CLOSE_ALL = 1           # FOHO_VOL_CLOSE_ALL
-_lib = None
+_i32, _i64, _rc = ctypes.c_int32, ctypes.c_int64, ctypes.c_int
+_SIGNATURES = {
+    "foho_vol_mark": (_rc, [vp, _i32, _i32, vp, vp, vp]), "foho_vol_select": (_rc, [vp, vp, _i32, vp, vp, vp]),
+    "foho_vol_close": (_rc, [vp, vp, _i32, _i32, vp, vp, vp, vp]), "foho_vol_count": (_rc, [vp, _i64, vp, vp, vp]),
+    "foho_vol_emit": (_rc, [vp, _i32, _i32, vp, vp, vp, vp, vp]), "foho_vol_fill": (_rc, [vp, _i32, vp, vp]),
+    "foho_vol_scatter": (_rc, [vp, vp, _i64, vp, vp]), "foho_vol_count_blocks": (_i64, [_i64])}
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(SO_PATH):
-            raise FohoError(f"{SO_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` (there is no CPU fallback)")
-        L = ctypes.CDLL(SO_PATH)
-        L.foho_vol_version.restype = ctypes.c_int
-        if L.foho_vol_version() != VERSION:
-            raise FohoError(f"{SO_PATH} is version {L.foho_vol_version()}, this binding is {VERSION}: rebuild (make -C followmyhold_amd/csrc)")
-        L.foho_vol_last_error.restype = ctypes.c_char_p
-        i32, i64 = ctypes.c_int32, ctypes.c_int64
-        sig = {"foho_vol_mark": [vp, i32, i32, vp, vp, vp], "foho_vol_select": [vp, vp, i32, vp, vp, vp],
-               "foho_vol_close": [vp, vp, i32, i32, vp, vp, vp, vp], "foho_vol_count": [vp, i64, vp, vp, vp],
-               "foho_vol_emit": [vp, i32, i32, vp, vp, vp, vp, vp], "foho_vol_fill": [vp, i32, vp, vp],
-               "foho_vol_scatter": [vp, vp, i64, vp, vp]}
-        for name, args in sig.items():
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = ctypes.c_int, args
-        L.foho_vol_count_blocks.restype, L.foho_vol_count_blocks.argtypes = ctypes.c_int64, [ctypes.c_int64]
-        _lib = L
-    return _lib
+    return L_.load_side("vol", _SIGNATURES)
 
 
 def _check(status, what):
-    if status != 0:
-        raise FohoError(f"{what} failed ({status}): {lib().foho_vol_last_error().decode()}")
-
-
-def _p(t):
-    return None if t is None else vp(t.data_ptr())
-
-
-def _stream(device):
-    return vp(torch.cuda.current_stream(device).cuda_stream)
+    L_.check_side(lib(), "foho_vol", status, what)
 
 
 def _mask(n, device, fill=0):

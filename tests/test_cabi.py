@@ -110,3 +110,135 @@ def test_missing_library_fails_loudly(monkeypatch, tmp_path):
     monkeypatch.setattr(L, "SO_PATH", str(tmp_path / "nope.so"))
     with pytest.raises(L.FohoError):
         L.lib()
+
+
+def _layout_queries():
+    """Every host-only size query of the four libraries at fixed shapes, and every foho_step_workspace_region."""
+    from followmyhold_amd import _lib as L, sparse_flexi, volume  # noqa: F401
+    from followmyhold_amd.geo_decode import FohoGeoWeights
+    from followmyhold_amd.vae_transformer import FohoVaeDesc, FohoVaeLayer
+    L.build()
+    lib = L.lib()
+    sz, i32, i64 = ctypes.c_size_t, ctypes.c_int32, ctypes.c_int64
+    got = {}
+
+    def dims(B, H, W, Vh, Vo, Fh, Fo, grid_res, frac_cap):
+        d = L.FohoDims()
+        d.B, d.H, d.W, d.Vtot, d.Ftot, d.Vmax, d.Fmax, d.Vh_max, d.Vo_max = B, H, W, B * (Vh + Vo), B * (Fh + Fo), Vh + Vo, Fh + Fo, Vh, Vo
+        d.grid_res, d.frac_cap, d.n_renders = grid_res, frac_cap, 2
+        return d
+
+    for tag, d in (("b2_512", dims(2, 512, 512, 778, 10242, 1552, 20480, 64, 1 << 18)), ("b1_64", dims(1, 64, 64, 778, 642, 1538, 1280, 16, 1 << 14))):
+        got[f"step/{tag}"] = lib.foho_step_workspace_bytes(ctypes.byref(d))
+        for i, name in enumerate(L.WS_REGIONS):
+            nb = i64(0)
+            got[f"step/{tag}/{name}"] = (lib.foho_step_workspace_region(ctypes.byref(d), i, ctypes.byref(nb)), nb.value)
+
+    def q(fn, argtypes, *args):
+        f = getattr(lib, fn)
+        f.restype, f.argtypes = sz, argtypes
+        return f(*args)
+
+    for res in (1, 8, 64, 384):
+        got[f"flexi/{res}"] = q("foho_flexi_workspace_bytes", [i32], res)
+    got["topology/11020"] = q("foho_topology_workspace_bytes", [i32], 11020)
+    got["raster/11020,22032,512,512"] = q("foho_raster_workspace_bytes", [i32] * 4, 11020, 22032, 512, 512)
+    got["icp/5000,10000"] = q("foho_icp_workspace_bytes", [i32] * 2, 5000, 10000)
+    got["sdpa/3072,3072,16"] = q("foho_sdpa_workspace_bytes", [i32] * 3, 3072, 3072, 16)
+    S = sparse_flexi.lib()
+    for res in (1, 13, 384):
+        got[f"sflexi_mark/{res}"] = S.foho_sflexi_mark_bytes(res)
+    for cap in (0, 1, 1000, 2_000_000):
+        got[f"sflexi_cube/{cap}"] = S.foho_sflexi_cube_bytes(cap)
+    for a in ((642, 1280, 64, 64, 8, 65536), (642, 1280, 37, 53, 100, 1000)):
+        got["rastk/" + ",".join(map(str, a))] = L.rastk().foho_rastk_workspace_bytes(*a)
+    # the geometry decoder and the VAE transformer: shapes only, every pointer non-null (test_geo_decode.py, test_vae_transformer.py)
+    for width, heads, n_lat, hidden, chunk, n in ((1024, 16, 3072, 4096, 16384, 65 ** 3), (128, 2, 128, 512, 512, 1000)):
+        w = FohoGeoWeights()
+        w.width, w.heads, w.n_latents, w.hidden, w.n_freqs = width, heads, n_lat, hidden, 8
+        for name, typ in FohoGeoWeights._fields_:
+            if typ is L.vp:
+                setattr(w, name, 1)
+        P = ctypes.POINTER(FohoGeoWeights)
+        got[f"geo/{width}"] = (q("foho_geo_workspace_bytes", [P, i32], ctypes.byref(w), chunk),
+                               q("foho_geo_bwd_workspace_bytes", [P, i32], ctypes.byref(w), chunk),
+                               q("foho_geo_saved_bytes", [P, i32, i64], ctypes.byref(w), chunk, n))
+    for width, heads, hidden, n_layers, tokens in ((1024, 16, 4096, 16, 3072), (128, 2, 512, 2, 128)):
+        layers = (FohoVaeLayer * n_layers)()
+        for y in layers:
+            for name, typ in FohoVaeLayer._fields_:
+                if typ is L.vp:
+                    setattr(y, name, 1)
+            y.eps1 = y.eps2 = 1e-6
+            y.qk_norm = 1
+        d = FohoVaeDesc()
+        d.width, d.heads, d.hidden, d.n_layers, d.n_tokens, d.batch = width, heads, hidden, n_layers, tokens, 1
+        d.layers = ctypes.cast(layers, ctypes.POINTER(FohoVaeLayer))
+        d.zeros = 1
+        P = ctypes.POINTER(FohoVaeDesc)
+        got[f"vae/{width}"] = (q("foho_vae_workspace_bytes", [P], ctypes.byref(d)), q("foho_vae_saved_bytes", [P], ctypes.byref(d)))
+    return got
+
+
+LAYOUT_PINS = {'step/b2_512': 211119104,
+ 'step/b2_512/world': (23804928, 264480),
+ 'step/b2_512/ndc': (24069632, 264480),
+ 'step/b2_512/vn': (24687104, 264480),
+ 'step/b2_512/p2f': (27596288, 4194304),
+ 'step/b2_512/zbuf': (31790592, 4194304),
+ 'step/b2_512/sdist': (35984896, 4194304),
+ 'step/b2_512/prod': (40179200, 4194304),
+ 'step/b2_512/knn_idx': (209558272, 88160),
+ 'step/b2_512/knn_d2': (209646592, 88160),
+ 'step/b2_512/gworld': (298240, 264480),
+ 'step/b2_512/frac_count': (98560, 16),
+ 'step/b2_512/stats': (209293056, 512),
+ 'step/b2_512/parity': (1092352, 270400),
+ 'step/b2_512/frag_count': (10819328, 4194304),
+ 'step/b2_512/seg_count': (98816, 181776),
+ 'step/b2_512/hand_order': (209734912, 6224),
+ 'step/b1_64': 11823616,
+ 'step/b1_64/world': (464384, 17040),
+ 'step/b1_64/ndc': (481536, 17040),
+ 'step/b1_64/vn': (521472, 17040),
+ 'step/b1_64/p2f': (708352, 32768),
+ 'step/b1_64/zbuf': (741120, 32768),
+ 'step/b1_64/sdist': (773888, 32768),
+ 'step/b1_64/prod': (806656, 32768),
+ 'step/b1_64/knn_idx': (11119616, 5680),
+ 'step/b1_64/knn_d2': (11125504, 5680),
+ 'step/b1_64/gworld': (23296, 17040),
+ 'step/b1_64/frac_count': (1024, 8),
+ 'step/b1_64/stats': (11102208, 256),
+ 'step/b1_64/parity': (74752, 9248),
+ 'step/b1_64/frag_count': (167936, 32768),
+ 'step/b1_64/seg_count': (1280, 12688),
+ 'step/b1_64/hand_order': (11131392, 3112),
+ 'flexi/1': 1792,
+ 'flexi/8': 23040,
+ 'flexi/64': 8953344,
+ 'flexi/384': 1879652864,
+ 'topology/11020': 89088,
+ 'raster/11020,22032,512,512': 51290112,
+ 'icp/5000,10000': 180992,
+ 'sdpa/3072,3072,16': 107151360,
+ 'sflexi_mark/1': 1024,
+ 'sflexi_mark/13': 1280,
+ 'sflexi_mark/384': 7963392,
+ 'sflexi_cube/0': 256,
+ 'sflexi_cube/1': 1536,
+ 'sflexi_cube/1000': 22784,
+ 'sflexi_cube/2000000': 44016384,
+ 'rastk/642,1280,64,64,8,65536': 319744,
+ 'rastk/642,1280,37,53,100,1000': 61440,
+ 'geo/1024': (268607744, 675282944, 5151653888),
+ 'geo/128': (1238272, 3350528, 2367488),
+ 'vae/1024': (208429056, 1613758464),
+ 'vae/128': (955392, 1050624)}
+
+
+def test_workspace_layouts_are_pinned():
+    """No workspace layout moves by a byte: the value of every size query and every region's (offset, size), as recorded from the commit
+    before the layouts went through the one allocator (csrc/foho_carve.h)."""
+    got = _layout_queries()
+    assert got == LAYOUT_PINS, {k: (got.get(k), LAYOUT_PINS.get(k)) for k in set(got) | set(LAYOUT_PINS) if got.get(k) != LAYOUT_PINS.get(k)}

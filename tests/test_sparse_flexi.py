@@ -299,8 +299,9 @@ def test_repeatable_and_stream_independent():
     assert a[0].shape[0] > 1000
 
 
-def _sparse_raw(ax, s, res, n_cubes, verts_cap, faces_cap, guard):
-    """foho_sflexi_mark + _extract through ctypes into buffers with `guard` extra elements of a known pattern behind each capacity."""
+def _sparse_raw(ax, s, res, n_cubes, verts_cap, faces_cap, guard, want_ldev=True):
+    """foho_sflexi_mark + _extract through ctypes into buffers with `guard` extra elements of a known pattern behind each capacity;
+    want_ldev False: a null l_dev (the buffer comes back untouched)."""
     L = SF.lib()
     st = vp(torch.cuda.current_stream().cuda_stream)
     nm = L.foho_sflexi_mark_bytes(res)
@@ -315,11 +316,12 @@ def _sparse_raw(ax, s, res, n_cubes, verts_cap, faces_cap, guard):
     ldev = torch.full((verts_cap + guard,), -7.5, device="cuda")
     counts = torch.full((3,), -1, dtype=torch.int32, device="cuda")
     assert L.foho_sflexi_extract(vp(ax.data_ptr()), vp(s.data_ptr()), res, vp(marks.data_ptr()), nm, n_cubes, vp(verts.data_ptr()), verts_cap,
-                                 vp(faces.data_ptr()), faces_cap, vp(ldev.data_ptr()), vp(counts.data_ptr()), vp(ws.data_ptr()), nw, st) == 0
+                                 vp(faces.data_ptr()), faces_cap, vp(ldev.data_ptr()) if want_ldev else None, vp(counts.data_ptr()), vp(ws.data_ptr()), nw,
+                                 st) == 0
     return verts, faces, ldev, counts.tolist()
 
 
-def _dense_raw(x, s, res, verts_cap, faces_cap, guard):
+def _dense_raw(x, s, res, verts_cap, faces_cap, guard, want_ldev=True):
     H = _lib.lib()
     H.foho_flexi_workspace_bytes.restype = ctypes.c_size_t
     nws = H.foho_flexi_workspace_bytes(res)
@@ -329,9 +331,30 @@ def _dense_raw(x, s, res, verts_cap, faces_cap, guard):
     ldev = torch.full((verts_cap + guard,), -7.5, device="cuda")
     counts = torch.zeros(3, dtype=torch.int32, device="cuda")
     _lib.check(H.foho_flexi_fwd(vp(x.data_ptr()), vp(s.data_ptr()), res, vp(verts.data_ptr()), verts_cap, vp(faces.data_ptr()), faces_cap,
-                                vp(ldev.data_ptr()), vp(counts.data_ptr()), vp(ws.data_ptr()), ctypes.c_size_t(nws),
+                                vp(ldev.data_ptr()) if want_ldev else None, vp(counts.data_ptr()), vp(ws.data_ptr()), ctypes.c_size_t(nws),
                                 vp(torch.cuda.current_stream().cuda_stream)), "foho_flexi_fwd")
     return verts, faces, ldev, counts.tolist()
+
+
+@gpu
+@pytest.mark.parametrize("want_ldev", [True, False])
+def test_all_codes_field_equals_dense_with_and_without_l_dev(want_ldev):
+    """Both extractors call one per-cube core (csrc/flexi_core.h); on the 9^3 field that shows all 256 corner codes they agree bit for bit
+    with l_dev requested and with a null l_dev, and a null l_dev leaves nothing written."""
+    res, guard = 8, 8
+    s = torch.from_numpy(_random_field(res)).cuda()
+    codes = _codes(s.cpu().numpy(), res)
+    n = int(((codes != 0) & (codes != 255)).sum())
+    vc, fc = 4 * n, 6 * n                  # at most 4 vertices and 6 triangles per surface cube
+    sv, sf_, sl, sc = _sparse_raw(SF.grid_axes(BMIN, BMAX, res).cuda(), s, res, n, vc, fc, guard, want_ldev)
+    dv, df, dl, dc = _dense_raw(_grid(res), s, res, vc, fc, guard, want_ldev)
+    nv, nf, over = sc
+    assert sc == dc and over == 0 and nv > n and nf > 0, (sc, dc)
+    assert torch.equal(sv[:nv * 3], dv[:nv * 3]) and torch.equal(sf_[:nf * 3], df[:nf * 3])
+    if want_ldev:
+        assert torch.equal(sl[:nv], dl[:nv]) and bool((sl[:nv] >= 0).all())
+    else:
+        assert bool((sl == -7.5).all()) and bool((dl == -7.5).all())
 
 
 @gpu
