@@ -617,7 +617,16 @@ __device__ __forceinline__ void plane_crossing_bwd(const float* p1, const float*
 }
 // eval_frag_bwd for a face that may straddle the near plane: the fragment's sub-triangle is found again with the forward
 // rule, differentiated, and its vertex gradients are pushed through the cut onto the face's own vertices (the cut moves
-// with them).  g_cin refers to the SUB-TRIANGLE's barycentrics (the fused step never sends gradient into barycentrics).
+// with them).
+// FACE_BARY = true (the exported operators k_raster_bwd_op / k_rk_bwd): g_cin is the gradient w.r.t. the barycentrics the
+// forward operators return, those of the UNCLIPPED face (subtri_bary_to_face).  On a clipped face it is carried through the
+// transpose of that conversion: b_face = P M^T b_sub, rows of M = the barycentrics of the sub-triangle's vertices in
+// (p1, p2, p3), p4 = (1 - w2, w2, 0), p5 = (1 - w3, 0, w3), P the rotation onto positions i1, i1 + 1, i1 + 2.  So
+// g_sub = M P^T g_face, and since w2, w3 move with the depths, g_w2 = b_sub[p4] (g_p2 - g_p1), g_w3 = b_sub[p5] (g_p3 - g_p1)
+// go to z1 and z_o with the factors of plane_crossing_bwd.
+// FACE_BARY = false (the fused step and the silhouette backward, which send zeros into barycentrics): g_cin is handed to
+// eval_frag_bwd as it is, i.e. it refers to the SUB-TRIANGLE's barycentrics, and none of the above is generated.
+template <bool FACE_BARY = false>
 __device__ __forceinline__ void eval_frag_near_bwd(const float* __restrict__ fv, float zc, float blur_radius, float sqrt_blur,
                                                    float xf, float yf, float g_z, const float* g_cin, float g_sd, float* gv) {
     // One straight path, no early returns: stores into gv[] from several exits get merged by the optimiser into ONE store
@@ -630,20 +639,46 @@ __device__ __forceinline__ void eval_frag_near_bwd(const float* __restrict__ fv,
     g.i1 = 0;
     g.w2 = g.w3 = 0.5f;
     bool second = false, live = true;
+    const float* gcp = g_cin;
+    float gcs[3], gw2 = 0.0f, gw3 = 0.0f;  // FACE_BARY only
+    if (FACE_BARY) {
+        _Pragma("unroll") for (int q = 0; q < 3; q++) gcs[q] = g_cin[q];
+        gcp = gcs;
+    }
     if (near) {
         g = clip_subtris(fv, zc, t0, t1);
         Frag f0, f1;
+        if (FACE_BARY) {
+            f0.z = f0.sdist = f0.c0 = f0.c1 = f0.c2 = 0.0f;  // read below through selects also where eval_frag rejected the half
+            f1 = f0;
+        }
         const bool r0 = g.n > 0 && eval_frag(t0, xf, yf, blur_radius, sqrt_blur, f0);
         const bool r1 = g.n == 2 && eval_frag(t1, xf, yf, blur_radius, sqrt_blur, f1);
         second = r1 && (!r0 || fabsf(f1.sdist) < fabsf(f0.sdist));
         live = r0 || r1;
+        if (FACE_BARY) {
+            // g_face at p1, p2, p3; at the crossings the conversion's rows blend them like the crossings blend the vertices
+            const bool s1 = g.i1 == 1, s2 = g.i1 == 2, one = g.n == 1;
+            const float h1 = s1 ? g_cin[1] : (s2 ? g_cin[2] : g_cin[0]), h2 = s1 ? g_cin[2] : (s2 ? g_cin[0] : g_cin[1]),
+                        h3 = s1 ? g_cin[0] : (s2 ? g_cin[1] : g_cin[2]);
+            const float h4 = (1.0f - g.w2) * h1 + g.w2 * h2, h5 = (1.0f - g.w3) * h1 + g.w3 * h3;
+            // (p4, p5, p1) | (p4, p2, p5) | (p5, p2, p3)
+            gcs[0] = live ? ((one || !second) ? h4 : h5) : 0.0f;
+            gcs[1] = live ? (one ? h5 : h2) : 0.0f;
+            gcs[2] = live ? (one ? h1 : (second ? h3 : h5)) : 0.0f;
+            // the sub-triangle's barycentrics at p4 / p5 (the forward's own values; 0 where the half does not hold the point)
+            const float c0 = second ? f1.c0 : f0.c0, c1 = second ? f1.c1 : f0.c1, c2 = second ? f1.c2 : f0.c2;
+            const float b4 = (one || !second) ? c0 : 0.0f, b5 = one ? c1 : (second ? c0 : c2);
+            gw2 = live ? b4 * (h2 - h1) : 0.0f;
+            gw3 = live ? b5 * (h3 - h1) : 0.0f;
+        }
     }
     float ts[9], gt[9];
     _Pragma("unroll") for (int q = 0; q < 9; q++) {
         ts[q] = second ? t1[q] : t0[q];
         gt[q] = 0.0f;
     }
-    eval_frag_bwd(ts, xf, yf, live ? g_z : 0.0f, g_cin, live ? g_sd : 0.0f, gt);
+    eval_frag_bwd(ts, xf, yf, live ? g_z : 0.0f, gcp, live ? g_sd : 0.0f, gt);
     float d[9];
     _Pragma("unroll") for (int q = 0; q < 9; q++) d[q] = gt[q];
     if (near) {
@@ -661,6 +696,12 @@ __device__ __forceinline__ void eval_frag_near_bwd(const float* __restrict__ fv,
         }
         plane_crossing_bwd(p1, p2, zc, g.w2, g4, g1, g2);
         plane_crossing_bwd(p1, p3, zc, g.w3, g5, g1, g3);
+        if (FACE_BARY) {  // w = (z1 - c) / (z1 - z_o): dw/dz1 = (c - z_o) / (z1 - z_o)^2, dw/dz_o = (z1 - c) / (z1 - z_o)^2
+            const float dz2 = p1[2] - p2[2], dz3 = p1[2] - p3[2], k2 = gw2 / (dz2 * dz2), k3 = gw3 / (dz3 * dz3);
+            g1[2] += k2 * (zc - p2[2]) + k3 * (zc - p3[2]);
+            g2[2] += k2 * (p1[2] - zc);
+            g3[2] += k3 * (p1[2] - zc);
+        }
         const bool r1 = g.i1 == 1, r2 = g.i1 == 2;
         _Pragma("unroll") for (int q = 0; q < 3; q++) {  // p1, p2, p3 back to positions i1, i1 + 1, i1 + 2 (mod 3)
             const float a = g1[q], b = g2[q], c = g3[q];

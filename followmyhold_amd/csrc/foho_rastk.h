@@ -70,8 +70,8 @@ FOHO_RASTK_API int foho_rastk_fwd(const float* verts_ndc, const int32_t* faces, 
                                   void* stream);
 
 /* grad_verts_ndc (V,3) += d(zbuf, bary, dists) / d verts_ndc of every one of the H W K fragments with pix_to_face >= 0: the
- * per-fragment derivative of foho_raster_bwd (for a face cut by the near plane the barycentric gradient refers to the
- * sub-triangle's barycentrics, and the cut moves with the vertices).  grad_zbuf, grad_dists: (H,W,K), grad_bary: (H,W,K,3); any
+ * per-fragment derivative of foho_raster_bwd (grad_bary refers to the barycentrics foho_rastk_fwd returns, the unclipped face's
+ * also on a face cut by the near plane; the cut and the conversion's crossing weights move with the vertices).  grad_zbuf, grad_dists: (H,W,K), grad_bary: (H,W,K,3); any
  * of the three may be NULL.  blur_radius: the forward call's. */
 FOHO_RASTK_API int foho_rastk_bwd(const float* verts_ndc, const int32_t* faces, int32_t V, int32_t F, int32_t H, int32_t W, int32_t K,
                                   const int64_t* pix_to_face, const float* grad_zbuf, const float* grad_bary, const float* grad_dists,

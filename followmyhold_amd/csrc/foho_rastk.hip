@@ -314,7 +314,7 @@ __global__ __launch_bounds__(TPB) void k_rk_bwd(const float* __restrict__ verts,
     const size_t pix = i / (size_t)K;
     const int py = (int)(pix / W), px = (int)(pix % W);
     const float gc[3] = {g_b ? g_b[3 * i] : 0.f, g_b ? g_b[3 * i + 1] : 0.f, g_b ? g_b[3 * i + 2] : 0.f};
-    eval_frag_near_bwd(fv, Z_CLIP, blur, sqrt_blur, pix_to_ndc(W - 1 - px, W, H), pix_to_ndc(H - 1 - py, H, W), g_z ? g_z[i] : 0.f, gc,
+    eval_frag_near_bwd<true>(fv, Z_CLIP, blur, sqrt_blur, pix_to_ndc(W - 1 - px, W, H), pix_to_ndc(H - 1 - py, H, W), g_z ? g_z[i] : 0.f, gc,
                        g_d ? g_d[i] : 0.f, gv);
     for (int k = 0; k < 3; k++)
         for (int q = 0; q < 3; q++)

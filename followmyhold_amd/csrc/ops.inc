@@ -163,8 +163,8 @@ __global__ __launch_bounds__(256) void k_raster_bwd_op(const float* verts_ndc, c
     }
     const int py = i / W, px = i % W;
     const float gc[3] = {g_b ? g_b[3 * (size_t)i] : 0.f, g_b ? g_b[3 * (size_t)i + 1] : 0.f, g_b ? g_b[3 * (size_t)i + 2] : 0.f};
-    // (for a face cut by the near plane the barycentric gradient is taken w.r.t. its sub-triangle's barycentrics)
-    eval_frag_near_bwd(fv, zclip, blur_radius, sqrt_blur, pix_to_ndc(W - 1 - px, W, H), pix_to_ndc(H - 1 - py, H, W), g_z ? g_z[i] : 0.f, gc,
+    // g_b refers to the barycentrics foho_raster_fwd returns: the unclipped face's, also where the near plane cuts the face
+    eval_frag_near_bwd<true>(fv, zclip, blur_radius, sqrt_blur, pix_to_ndc(W - 1 - px, W, H), pix_to_ndc(H - 1 - py, H, W), g_z ? g_z[i] : 0.f, gc,
                        g_d ? g_d[i] : 0.f, gv);
     for (int k = 0; k < 3; k++)
         for (int q = 0; q < 3; q++)

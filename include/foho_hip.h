@@ -255,8 +255,9 @@ FOHO_API int foho_raster_fwd(const float* verts_ndc, const int32_t* faces, int32
                     float* sil_prod, int32_t* overflow_flag, void* workspace, size_t workspace_bytes, void* stream);
 FOHO_API size_t foho_raster_workspace_bytes(int32_t V, int32_t F, int32_t H, int32_t W);
 /* backward of the K=1 fragments: grad_verts_ndc (V,3) += d(zbuf,bary,dists)/d verts_ndc.  blur_radius = the forward
- * call's (it decides which half of a near-clipped face left a fragment; for such faces grad_bary is taken w.r.t. the
- * sub-triangle's barycentrics) */
+ * call's (it decides which half of a near-clipped face left a fragment).  grad_bary refers to the barycentrics
+ * foho_raster_fwd returns -- the unclipped face's, also on a face the near plane cuts: the conversion from the sub-triangle's
+ * and its crossing weights are differentiated with the rest */
 FOHO_API int foho_raster_bwd(const float* verts_ndc, const int32_t* faces, int32_t V, int32_t F, int32_t H, int32_t W,
                     const int64_t* pix_to_face, const float* grad_zbuf, const float* grad_bary,
                     const float* grad_dists, float* grad_verts_ndc, float blur_radius, void* stream);
