@@ -72,7 +72,7 @@ ABI_VERSION = 105     # 105 = foho_vae_fwd / _bwd, foho_geo_weights.flags, foho_
 
 
 # the side libraries: libfoho_<name>.so exports foho_<name>_* (C ABI csrc/foho_<name>.h) and is of version FOHO_<NAME>_VERSION
-SIDE_VERSIONS = {"vol": 100, "sflexi": 100, "rastk": 100}
+SIDE_VERSIONS = {"vol": 100, "sflexi": 100, "rastk": 101}      # rastk 101 = foho_rastk_blend_fwd / _bwd
 _sides = {}
 
 
@@ -172,7 +172,12 @@ RASTK_SO_PATH = side_path("rastk")
 RASTK_VERSION = SIDE_VERSIONS["rastk"]      # FOHO_RASTK_VERSION of csrc/foho_rastk.h
 RASTK_MAX_K = 128        # FOHO_RASTK_MAX_K
 RASTK_CULL_BACKFACES, RASTK_OVER_LIST = 1, 1
+RASTK_BLEND_MAX_D = 4    # FOHO_RASTK_BLEND_MAX_D
+RASTK_BLEND_UNIT_BARY, RASTK_BLEND_ALPHA_ONLY = 1, 2
+_RASTK_BLEND_HEAD = [vp, vp, vp, vp, vp, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f, vp, c_i]     # planes, face_attr, F H W K D, sigma gamma znear zfar, background, flags
 _RASTK_SIGNATURES = {
+    "foho_rastk_blend_fwd": (ctypes.c_int, _RASTK_BLEND_HEAD + [vp, vp]),
+    "foho_rastk_blend_bwd": (ctypes.c_int, _RASTK_BLEND_HEAD + [vp, vp, vp, vp, vp, vp]),
     "foho_rastk_workspace_bytes": (ctypes.c_size_t, [c_i, c_i, c_i, c_i, c_i, ctypes.c_int64]),
     "foho_rastk_fwd": (ctypes.c_int, [vp, vp, c_i, c_i, c_i, c_i, c_i, c_f, c_i, vp, vp, vp, vp, vp, vp, ctypes.c_int64, vp, ctypes.c_size_t, vp]),
     "foho_rastk_bwd": (ctypes.c_int, [vp, vp, c_i, c_i, c_i, c_i, c_i, vp, vp, vp, vp, vp, c_f, vp])}

@@ -41,11 +41,15 @@
 extern "C" {
 #endif
 
-#define FOHO_RASTK_VERSION 100
+#define FOHO_RASTK_VERSION 101 /* 101 = foho_rastk_blend_fwd / _bwd */
 #define FOHO_RASTK_MAX_K 128
 #define FOHO_RASTK_MAX_LIST (1 << 30) /* entries of the packed tile lists */
-/* flags */
+#define FOHO_RASTK_BLEND_MAX_D 4 /* channels of the face attributes foho_rastk_blend_* takes */
+/* flags of foho_rastk_fwd */
 #define FOHO_RASTK_CULL_BACKFACES 1
+/* flags of foho_rastk_blend_fwd / _bwd */
+#define FOHO_RASTK_BLEND_UNIT_BARY 1  /* weights (1, 1, 1) in place of the barycentrics (PhongNormalShader); bary may be NULL */
+#define FOHO_RASTK_BLEND_ALPHA_ONLY 2 /* the silhouette alpha alone: out is (H,W); face_attr, zbuf, bary, background may be NULL */
 /* bits of *overflow */
 #define FOHO_RASTK_OVER_LIST 1 /* the tile lists need more than list_cap entries: no output was written */
 
@@ -76,6 +80,40 @@ FOHO_RASTK_API int foho_rastk_fwd(const float* verts_ndc, const int32_t* faces, 
 FOHO_RASTK_API int foho_rastk_bwd(const float* verts_ndc, const int32_t* faces, int32_t V, int32_t F, int32_t H, int32_t W, int32_t K,
                                   const int64_t* pix_to_face, const float* grad_zbuf, const float* grad_bary, const float* grad_dists,
                                   float* grad_verts_ndc, float blur_radius, void* stream);
+
+/* interpolate_face_attributes + softmax_rgb_blend (pytorch3d.renderer.blending) over K planes, one launch; no workspace, no
+ * allocation, no host read of device memory.  Per pixel, over its fragments k:
+ *   p_k = sigmoid(-dists_k / sigma)                        alpha = 1 - prod_k (1 - p_k)
+ *   zinv_k = (zfar - zbuf_k) / (zfar - znear)              m = max(max_k zinv_k, 1e-10)
+ *   w_k = p_k exp((zinv_k - m) / gamma)                    delta = max(exp((1e-10 - m) / gamma), 1e-10)
+ *   c_k = sum_j bary_kj face_attr[pix_to_face_k, j, :]     rgb = (sum_k w_k c_k + delta background) / (sum_k w_k + delta)
+ * pix_to_face: int64 (H,W,K); zbuf, dists: float32 (H,W,K); bary: (H,W,K,3); face_attr: (F,3,D) float32, 1 <= D <=
+ * FOHO_RASTK_BLEND_MAX_D; background: D floats in HOST memory, read at call time; out: (H,W,D+1) float32, the D blended channels, then
+ * alpha.  With FOHO_RASTK_BLEND_ALPHA_ONLY out is (H,W) alpha, F, gamma, znear, zfar are not used, and D is any legal value.
+ *
+ * CONTRACT ON THE PLANES: they are FRONT-PACKED, as foho_rastk_fwd writes them -- a pixel's fragments are its leading entries with
+ * an id >= 0.  Everything from the first negative id on is ignored, whatever it holds (other ids, NaN), and receives no gradient;
+ * planes with a valid entry behind a negative one are not pytorch3d's masked blend.  An id >= F ends the pixel's fragments like a
+ * negative one (no face attribute is read out of range).  A pixel without a fragment gives rgb = background, alpha = 0.
+ *
+ * Refused with a negative status, never clamped: K outside 1 .. FOHO_RASTK_MAX_K, D outside 1 .. FOHO_RASTK_BLEND_MAX_D, F, H or W out
+ * of foho_rastk_workspace_bytes' range, sigma <= 0, gamma <= 0, zfar <= znear, an unknown flag bit, a NULL required pointer. */
+FOHO_RASTK_API int foho_rastk_blend_fwd(const int64_t* pix_to_face, const float* zbuf, const float* bary, const float* dists,
+                                        const float* face_attr, int32_t F, int32_t H, int32_t W, int32_t K, int32_t D, float sigma,
+                                        float gamma, float znear, float zfar, const float* background, int32_t flags, float* out,
+                                        void* stream);
+
+/* The derivative of foho_rastk_blend_fwd, the clamps and the max followed as written (the gradient through m goes to the FIRST fragment
+ * of the largest zinv; where delta is clamped m does not cancel).  grad_out: (H,W,D+1), or (H,W) with FOHO_RASTK_BLEND_ALPHA_ONLY.
+ * grad_zbuf, grad_dists: (H,W,K), grad_bary: (H,W,K,3), grad_face_attr: (F,3,D); any of the four may be NULL (with
+ * FOHO_RASTK_BLEND_UNIT_BARY grad_bary is not written, with FOHO_RASTK_BLEND_ALPHA_ONLY only grad_dists is).  The three plane gradients
+ * are WRITTEN, at the pixel's fragments only: the caller supplies zeroed buffers.  grad_face_attr is ADDED to with float atomics, like
+ * foho_rastk_bwd's vertex gradient; everything else has one owner thread per entry and is bitwise repeatable. */
+FOHO_RASTK_API int foho_rastk_blend_bwd(const int64_t* pix_to_face, const float* zbuf, const float* bary, const float* dists,
+                                        const float* face_attr, int32_t F, int32_t H, int32_t W, int32_t K, int32_t D, float sigma,
+                                        float gamma, float znear, float zfar, const float* background, int32_t flags,
+                                        const float* grad_out, float* grad_zbuf, float* grad_bary, float* grad_dists,
+                                        float* grad_face_attr, void* stream);
 
 #ifdef __cplusplus
 }

@@ -11,6 +11,7 @@
 //                 [slot][lane] (8-byte words, lane contiguous: conflict free), its current maximum in registers; then the lane
 //                 sorts its column, re-evaluates the kept fragments from their keys and writes the planes
 //   k_rk_bwd      one thread per (pixel, k): foho_raster_bwd's derivative, float atomicAdd into the vertex gradient
+//   k_rk_blend_*  rastk_blend.inc: the consumer of the planes, shading and softmax blend with gradient, one thread per pixel
 // Compiled with foho_step.hip's flags (-ffp-contract=off, correctly rounded division and sqrt): the per-(pixel, face) arithmetic is
 // foho_common.h's eval_frag / clip_subtris / subtri_bary_to_face, the functions k_raster.inc's evaluate stage and k_raster_export
 // call, and that arithmetic decides face ids.
@@ -383,3 +384,5 @@ FOHO_RASTK_API int foho_rastk_bwd(const float* verts_ndc, const int32_t* faces, 
 }
 
 }  // extern "C"
+
+#include "rastk_blend.inc"  // foho_rastk_blend_fwd / _bwd

@@ -7,7 +7,8 @@ The reference's patched pipeline talks to its geometry libraries through a small
 1324-1336, 1529-1553; run.py:84-116).  This module answers that surface with N=1 batches (the reference's
 batch size, guid_config.py:9).  Rasterisation, nearest neighbours and the SDF pieces are HIP operators behind
 torch.autograd.Functions; the glue the reference itself writes in torch (shader blend, normalisation) stays in
-torch ops on the device.  For throughput use followmyhold_amd.engine.GuidanceBatch (the fused step) instead.
+torch ops on the device -- unless BlendParams(fused=True) sends K-fragment planes through ops.blend_k / blend_k_alpha (one launch
+each way).  For throughput use followmyhold_amd.engine.GuidanceBatch (the fused step) instead.
 
 The K=100 silhouette alpha is differentiable (foho_raster_sil_bwd: through every fragment of the pixels with fractional
 coverage); its sigma comes from the shader's blend_params.
@@ -128,8 +129,11 @@ class FoVPerspectiveCameras:
 
 
 class BlendParams:
-    def __init__(self, sigma=1e-4, gamma=1e-4, background_color=(1.0, 1.0, 1.0)):
+    def __init__(self, sigma=1e-4, gamma=1e-4, background_color=(1.0, 1.0, 1.0), fused=False):
         self.sigma, self.gamma, self.background_color = float(sigma), float(gamma), background_color
+        # fused=True: the shaders blend K-fragment planes (RasterizationSettings(k_fragments=True)) with ops.blend_k / blend_k_alpha,
+        # one launch each way, and refuse other planes.  False (default): the torch blend below, on whatever planes arrive.
+        self.fused = bool(fused)
 
 
 class RasterizationSettings:
@@ -145,8 +149,9 @@ class RasterizationSettings:
 
 
 class Fragments:
-    def __init__(self, pix_to_face, zbuf, bary_coords, dists, sil_prod=None):
+    def __init__(self, pix_to_face, zbuf, bary_coords, dists, sil_prod=None, k_planes=False):
         self.pix_to_face, self.zbuf, self.bary_coords, self.dists, self.sil_prod = pix_to_face, zbuf, bary_coords, dists, sil_prod
+        self.k_planes = bool(k_planes)      # the planes came from the k_fragments branch: (1, H, W, K), front-packed, -1 padded
 
 
 class _RasterFn(torch.autograd.Function):
@@ -193,7 +198,7 @@ class MeshRasterizer:
         if rs.k_fragments:
             p2f, z, b, d, _ = ops.raster_k(ndc, meshes.faces_packed().contiguous(), H, W, rs.faces_per_pixel, rs.blur_radius,
                                            rs.cull_backfaces)
-            return Fragments(p2f[None], z[None], b[None], d[None], None)
+            return Fragments(p2f[None], z[None], b[None], d[None], None, k_planes=True)
         want_sil = rs.faces_per_pixel > 1
         # sigma of the silhouette product: the renderer hands over its shader's blend_params.sigma; a bare rasteriser call
         # takes the sigma its blur radius was derived from (blur_radius = log(1 / 1e-4 - 1) sigma, RUN:97)
@@ -231,6 +236,25 @@ def softmax_rgb_blend(colors, fragments, blend_params, znear=1.0, zfar=100.0):
     return torch.cat([rgb, (1.0 - alpha)[..., None]], dim=-1)
 
 
+def _fused_planes(fragments, blend_params):
+    """True when blend_params asks for the fused blend; the planes must then be K-fragment planes."""
+    if not getattr(blend_params, "fused", False):
+        return False
+    if not getattr(fragments, "k_planes", False):
+        raise ValueError("BlendParams(fused=True) needs the planes of RasterizationSettings(k_fragments=True)")
+    return True
+
+
+def blend_fragments(fragments, face_attributes, blend_params, znear=1.0, zfar=100.0):
+    """interpolate_face_attributes + softmax_rgb_blend for a caller's own (F,3,D) face attributes: (1, H, W, D+1).  With
+    blend_params.fused on K-fragment planes one ops.blend_k launch (1 <= D <= 4, D background entries); otherwise the torch route."""
+    if _fused_planes(fragments, blend_params):
+        return ops.blend_k(fragments.pix_to_face[0], fragments.zbuf[0], fragments.bary_coords[0], fragments.dists[0], face_attributes,
+                           blend_params.sigma, blend_params.gamma, znear, zfar, blend_params.background_color)[None]
+    colors = interpolate_face_attributes(fragments.pix_to_face, fragments.bary_coords, face_attributes)
+    return softmax_rgb_blend(colors, fragments, blend_params, znear=znear, zfar=zfar)
+
+
 class ShaderBase:
     def __init__(self, device="cpu", cameras=None, lights=None, materials=None, blend_params=None):
         self.cameras, self.blend_params = cameras, blend_params or BlendParams()
@@ -250,6 +274,9 @@ class PhongNormalShader(ShaderBase):
         blend_params = kwargs.get("blend_params", self.blend_params)
         faces = meshes.faces_packed()
         faces_normals = meshes.verts_normals_packed()[faces]
+        if _fused_planes(fragments, blend_params):      # weights (1, 1, 1) inside the kernel: no tensor of ones, no (H,W,K,3,3) gather
+            return ops.blend_k(fragments.pix_to_face[0], fragments.zbuf[0], None, fragments.dists[0], faces_normals, blend_params.sigma,
+                               blend_params.gamma, cameras.znear, cameras.zfar, blend_params.background_color, unit_bary=True)[None]
         ones = torch.ones_like(fragments.bary_coords)
         pixel_normals = interpolate_face_attributes(fragments.pix_to_face, ones, faces_normals)
         return softmax_rgb_blend(pixel_normals, fragments, blend_params, znear=cameras.znear, zfar=cameras.zfar)
@@ -259,11 +286,16 @@ class SoftSilhouetteShader(ShaderBase):
     """alpha = 1 - prod_k(1 - sigmoid(-d_k / sigma)) over the K nearest fragments (run.py:113-116)."""
 
     def forward(self, fragments, meshes, **kwargs):
+        fused = _fused_planes(fragments, kwargs.get("blend_params", self.blend_params))
         if fragments.sil_prod is None:
             if fragments.pix_to_face.shape[-1] <= 1:
                 raise ValueError("SoftSilhouetteShader needs a rasterizer with faces_per_pixel > 1")
-            # K-fragment planes (RasterizationSettings(k_fragments=True)): the product over the K layers, in torch
+            # K-fragment planes (RasterizationSettings(k_fragments=True)): the product over the K layers, fused or in torch
             blend_params = kwargs.get("blend_params", self.blend_params)
+            if fused:
+                a = ops.blend_k_alpha(fragments.pix_to_face[0], fragments.dists[0], blend_params.sigma)[None]
+                rgb = torch.ones(a.shape + (3,), device=a.device, dtype=a.dtype)
+                return torch.cat([rgb, a[..., None]], dim=-1)
             mask = fragments.pix_to_face >= 0
             a = 1.0 - torch.prod(1.0 - torch.sigmoid(-fragments.dists / blend_params.sigma) * mask, dim=-1)
             rgb = torch.ones(a.shape + (3,), device=a.device, dtype=a.dtype)

@@ -177,6 +177,120 @@ def raster_k(verts_ndc, faces, H, W, K, blur_radius, cull_backfaces=False):
     return _RasterKFn.apply(verts_ndc, faces, int(H), int(W), int(K), float(blur_radius), bool(cull_backfaces))
 
 
+# ------------------------------------------------------------------------------------------------ shading + blend of K-fragment planes
+def _blend_k_args(pix_to_face, zbuf, bary, dists, face_attr, sigma, gamma, znear, zfar, background, unit_bary, alpha_only, grad_out=None):
+    """Argument checks of blend_k_fwd / blend_k_bwd, before any device work.  Returns (H, W, K, D, F, flags, background array)."""
+    if pix_to_face.dim() != 3 or pix_to_face.dtype != torch.int64:
+        raise ValueError("blend_k: pix_to_face must be (H,W,K) int64")
+    H, W, K = pix_to_face.shape
+    if K < 1 or K > L.RASTK_MAX_K:
+        raise ValueError(f"blend_k: K = {K} outside 1 .. {L.RASTK_MAX_K} (not clamped)")
+    if H < 1 or W < 1 or H > 8192 or W > 8192 or H * W > (1 << 25):
+        raise ValueError(f"blend_k: frame {H} x {W} out of range")
+    planes = [("dists", dists, (H, W, K))]
+    if not alpha_only:
+        planes.append(("zbuf", zbuf, (H, W, K)))
+        if not unit_bary:
+            planes.append(("bary", bary, (H, W, K, 3)))
+    for name, t, shape in planes:
+        if t is None or tuple(t.shape) != shape or t.dtype != torch.float32:
+            raise ValueError(f"blend_k: {name} must be a float32 tensor of shape {shape}")
+    if not float(sigma) > 0.0:
+        raise ValueError("blend_k: sigma must be positive")
+    D, F, bg = 1, 1, None
+    if not alpha_only:
+        if face_attr is None or face_attr.dim() != 3 or face_attr.shape[1] != 3 or face_attr.dtype != torch.float32 or not len(face_attr):
+            raise ValueError("blend_k: face_attr must be a float32 tensor of shape (F,3,D)")
+        F, _, D = face_attr.shape
+        if D < 1 or D > L.RASTK_BLEND_MAX_D:
+            raise ValueError(f"blend_k: D = {D} outside 1 .. {L.RASTK_BLEND_MAX_D}")
+        if not float(gamma) > 0.0 or not float(zfar) > float(znear):
+            raise ValueError("blend_k: gamma must be positive and zfar above znear")
+        bg = [float(x) for x in (background.tolist() if torch.is_tensor(background) else background)]
+        if len(bg) != D:
+            raise ValueError(f"blend_k: background has {len(bg)} entries, the face attributes {D} channels")
+        bg = (ctypes.c_float * D)(*bg)
+    if grad_out is not None and tuple(grad_out.shape) != ((H, W) if alpha_only else (H, W, D + 1)):
+        raise ValueError(f"blend_k_bwd: grad_out of shape {tuple(grad_out.shape)}")
+    _need_cuda(grad_out, pix_to_face, dists, None if alpha_only else zbuf, None if alpha_only or unit_bary else bary, None if alpha_only else face_attr)
+    flags = (L.RASTK_BLEND_UNIT_BARY if unit_bary else 0) | (L.RASTK_BLEND_ALPHA_ONLY if alpha_only else 0)
+    return H, W, K, D, F, flags, bg
+
+
+def _blend_k_head(pix_to_face, zbuf, bary, dists, face_attr, sigma, gamma, znear, zfar, background, unit_bary, alpha_only, grad_out=None):
+    """The checked arguments both entry points of the library share (its C order) and the tensors they point into."""
+    H, W, K, D, F, flags, bg = _blend_k_args(pix_to_face, zbuf, bary, dists, face_attr, sigma, gamma, znear, zfar, background, unit_bary,
+                                             alpha_only, grad_out)
+    keep = [pix_to_face.contiguous(), None if alpha_only else zbuf.detach().contiguous(),
+            None if alpha_only or unit_bary else bary.detach().contiguous(), dists.detach().contiguous(),
+            None if alpha_only else face_attr.detach().contiguous()]
+    head = [L._p(t) for t in keep] + [F, H, W, K, D, float(sigma), float(gamma), float(znear), float(zfar), bg, flags]
+    return (H, W, K, D, F), head, keep
+
+
+def blend_k_fwd(pix_to_face, zbuf, bary, dists, face_attr, sigma, gamma, znear, zfar, background, unit_bary=False, alpha_only=False):
+    """facade.interpolate_face_attributes + softmax_rgb_blend over the (H,W,K) planes of raster_k_fwd in one launch (libfoho_rastk.so).
+    face_attr (F,3,D) float32, 1 <= D <= 4; background: D floats.  Returns (H,W,D+1): the D blended channels, then the alpha
+    1 - prod_k(1 - sigmoid(-dists_k / sigma)).  unit_bary: weights (1, 1, 1) in place of the barycentrics (bary may be None).
+    alpha_only: (H,W) alpha from pix_to_face and dists alone (every other tensor may be None).
+    The planes are front-packed, as raster_k_fwd writes them: everything from a pixel's first negative id on is ignored."""
+    (H, W, K, D, F), head, keep = _blend_k_head(pix_to_face, zbuf, bary, dists, face_attr, sigma, gamma, znear, zfar, background, unit_bary,
+                                                alpha_only)
+    out = torch.empty((H, W) if alpha_only else (H, W, D + 1), device=dists.device)
+    L.rastk_check(L.rastk().foho_rastk_blend_fwd(*head, P(out.data_ptr()), _stream(dists)), "foho_rastk_blend_fwd")
+    return out
+
+
+def blend_k_bwd(pix_to_face, zbuf, bary, dists, face_attr, sigma, gamma, znear, zfar, background, grad_out, unit_bary=False,
+                alpha_only=False, need=(True, True, True, True)):
+    """Backward of blend_k_fwd: (grad_zbuf, grad_bary, grad_dists, grad_face_attr), None where `need` is False (the library is
+    handed a null pointer and skips that output) and where the mode has no such input (unit_bary: bary; alpha_only: all but dists)."""
+    (H, W, K, D, F), head, keep = _blend_k_head(pix_to_face, zbuf, bary, dists, face_attr, sigma, gamma, znear, zfar, background, unit_bary,
+                                                alpha_only, grad_out)
+    go = _f32(grad_out)
+    dev = dists.device
+    need = [bool(n) for n in need]
+    if alpha_only:
+        need[0] = need[1] = need[3] = False
+    if unit_bary:
+        need[1] = False
+    # the plane gradients are written at the pixels' fragments only: zeroed buffers
+    shapes = ((H, W, K), (H, W, K, 3), (H, W, K), (F, 3, D))
+    grads = [torch.zeros(s, device=dev) if n else None for s, n in zip(shapes, need)]
+    L.rastk_check(L.rastk().foho_rastk_blend_bwd(*head, P(go.data_ptr()), *[L._p(g) for g in grads], _stream(dists)), "foho_rastk_blend_bwd")
+    return tuple(grads)
+
+
+class _BlendKFn(torch.autograd.Function):
+    """blend_k_fwd / blend_k_bwd as one differentiable operator (w.r.t. zbuf, bary, dists and face_attr)."""
+
+    @staticmethod
+    def forward(ctx, pix_to_face, zbuf, bary, dists, face_attr, cfg):
+        ctx.cfg = cfg
+        ctx.save_for_backward(pix_to_face, zbuf, bary, dists, face_attr)
+        return blend_k_fwd(pix_to_face, zbuf, bary, dists, face_attr, *cfg)
+
+    @staticmethod
+    def backward(ctx, g_out):
+        g = blend_k_bwd(*ctx.saved_tensors, *ctx.cfg[:5], g_out, *ctx.cfg[5:], need=ctx.needs_input_grad[1:5])
+        return (None,) + g + (None,)
+
+
+def blend_k(pix_to_face, zbuf, bary, dists, face_attr, sigma, gamma, znear, zfar, background, unit_bary=False):
+    """blend_k_fwd, differentiable w.r.t. zbuf, bary, dists and face_attr; the backward computes only the gradients autograd asks for.
+    Chained behind raster_k the gradient reaches the vertices through raster_k_bwd."""
+    bg = tuple(float(x) for x in (background.tolist() if torch.is_tensor(background) else background))
+    cfg = (float(sigma), float(gamma), float(znear), float(zfar), bg, bool(unit_bary), False)
+    return _BlendKFn.apply(pix_to_face, zbuf, None if unit_bary else bary, dists, face_attr, cfg)
+
+
+def blend_k_alpha(pix_to_face, dists, sigma):
+    """(H,W) alpha = 1 - prod_k(1 - sigmoid(-dists_k / sigma)) over the pixel's fragments (SoftSilhouetteShader on K-fragment planes),
+    differentiable w.r.t. dists.  Bitwise the last channel of blend_k."""
+    cfg = (float(sigma), 1.0, 0.0, 1.0, None, False, True)
+    return _BlendKFn.apply(pix_to_face, None, None, dists, None, cfg)
+
+
 # ------------------------------------------------------------------------------------------------ knn / sdf
 def knn1(p1, p2):
     """pytorch3d.ops.knn_points(K=1): (squared distances (N1,), indices (N1,) int64)."""

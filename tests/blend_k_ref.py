@@ -1,0 +1,121 @@
+"""Planes, referee and measure for tests/test_blend_k.py (ops.blend_k / blend_k_alpha, foho_rastk_blend_fwd / _bwd).
+
+Referee: the facade's own torch route -- interpolate_face_attributes + softmax_rgb_blend, or for the alpha-only form the product of
+SoftSilhouetteShader -- in float64 with autograd on the same planes.  Yardstick: the same route in float32 against the referee.
+Measure, per tensor: max |got - ref| / max |ref|.  Bound: 4 x yardstick (the project's margin for float-atomic reorderings), floored
+at 16 float32 ulps (a yardstick that happens to be 0, and the few-ulp freedom of exp).  Planes are built on the host from fixed seeds;
+the routes run on the device the caller names and are computed once per (planes, device, dtype)."""
+import functools
+
+import numpy as np
+import torch
+
+from followmyhold_amd import facade as p3d
+
+FLOOR = 16 * 2.0 ** -23                 # 1.9e-6
+ZNEAR, ZFAR = 0.01, 100.0
+REGIMES = [(1e-4, 1e-4), (1e-4, 0.1), (1e-3, 1.0)]       # (sigma, gamma): delta clamped on every hit pixel in the first, on none in the others
+FRAME = (5, 67)                          # neither a multiple of a wave nor of a tile
+N_FACES = 37
+NAMES = ("out", "grad_zbuf", "grad_bary", "grad_dists", "grad_face_attr")
+
+
+def relerr(got, ref):
+    return float((got.detach().double().cpu() - ref.detach().double().cpu()).abs().max() / ref.detach().double().abs().max().cpu())
+
+
+def bound(yardstick):
+    return max(4.0 * yardstick, FLOOR)
+
+
+@functools.lru_cache(maxsize=None)
+def constructed(K, D, sigma, seed=0):
+    """Front-packed planes on FRAME without a rasteriser: per-pixel fragment counts cycle through 0, 1, K - 1, K and a random count;
+    depths strictly increasing and tie-free in [1, 3); distances sigma * N(1.5, 2) (both signs, sigmoid neither 0 nor 1); barycentrics
+    positive with sum 1; ids in 0 .. N_FACES-1; padding -1.  Also random attributes, background and grad_out.  All float32 / int64, CPU."""
+    H, W = FRAME
+    rng = np.random.default_rng(1000 * K + 10 * D + seed)
+    pick = np.arange(H * W) % 5
+    counts = np.select([pick == 0, pick == 1, pick == 2, pick == 3], [0, min(1, K), K - 1, K], rng.integers(0, K + 1, H * W)).reshape(H, W)
+    valid = np.arange(K)[None, None, :] < counts[..., None]
+    z = rng.uniform(1.0, 2.0, (H, W, 1)) + np.cumsum(rng.uniform(5e-4, 2e-3, (H, W, K)), -1)
+    d = sigma * rng.normal(1.5, 2.0, (H, W, K))
+    b = rng.uniform(0.05, 1.0, (H, W, K, 3))
+    b /= b.sum(-1, keepdims=True)
+    ids = rng.integers(0, N_FACES, (H, W, K))
+    f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a.astype(np.float32)))
+    planes = dict(pix_to_face=torch.from_numpy(np.where(valid, ids, -1).astype(np.int64)), zbuf=f32(np.where(valid, z, -1.0)),
+                  bary=f32(np.where(valid[..., None], b, -1.0)), dists=f32(np.where(valid, d, -1.0)))
+    return dict(planes, counts=counts, face_attr=f32(rng.normal(size=(N_FACES, 3, D))), background=tuple(float(np.float32(x)) for x in rng.uniform(0, 1, D)),
+                grad_out=f32(rng.normal(size=(H, W, D + 1))))
+
+
+@functools.lru_cache(maxsize=None)
+def saturated(sigma=1e-4, seed=7):
+    """K = 4 planes on FRAME, every pixel full.  Pixels p % 3 == 0 hold two layers at d = -30 sigma (1 - sigmoid == 0 exactly in
+    float32) -- every fourth of them a third; p % 3 == 1 hold exactly one; p % 3 == 2 none.  On every seventh pixel one further layer
+    is at |d| / sigma = 1e6, alternating in sign.  The other layers: sigma * N(1.5, 2)."""
+    c = dict(constructed(4, 3, sigma, seed))
+    H, W = FRAME
+    p = np.arange(H * W).reshape(H, W)
+    c["pix_to_face"] = c["pix_to_face"].clamp(min=0)                 # every entry is a fragment
+    rng = np.random.default_rng(seed)
+    z = rng.uniform(1.0, 2.0, (H, W, 1)) + np.cumsum(rng.uniform(5e-4, 2e-3, (H, W, 4)), -1)
+    d = (sigma * rng.normal(1.5, 2.0, (H, W, 4))).astype(np.float32)
+    b = rng.uniform(0.05, 1.0, (H, W, 4, 3))
+    d[..., 0] = np.where(p % 3 <= 1, -30 * sigma, d[..., 0])
+    d[..., 2] = np.where(p % 3 == 0, -30 * sigma, d[..., 2])
+    d[..., 1] = np.where(p % 12 == 0, -30 * sigma, d[..., 1])
+    d[..., 3] = np.where(p % 7 == 0, np.where(p % 14 == 0, 1e6, -1e6) * sigma, d[..., 3])
+    c["zbuf"] = torch.from_numpy(z.astype(np.float32))
+    c["bary"] = torch.from_numpy((b / b.sum(-1, keepdims=True)).astype(np.float32))
+    c["dists"] = torch.from_numpy(d.astype(np.float32))
+    c["counts"] = np.full((H, W), 4)
+    return c
+
+
+def torch_route(planes, face_attr, background, sigma, gamma, dtype, unit_bary=False, znear=ZNEAR, zfar=ZFAR):
+    """The facade's torch blend on (H,W,K) planes: (H,W,D+1) in `dtype` (the planes may carry autograd history)."""
+    frag = p3d.Fragments(planes["pix_to_face"][None], planes["zbuf"].to(dtype)[None], planes["bary"].to(dtype)[None],
+                         planes["dists"].to(dtype)[None], None)
+    bary = torch.ones_like(frag.bary_coords) if unit_bary else frag.bary_coords
+    colors = p3d.interpolate_face_attributes(frag.pix_to_face, bary, face_attr.to(dtype))
+    return p3d.softmax_rgb_blend(colors, frag, p3d.BlendParams(sigma, gamma, background), znear=znear, zfar=zfar)[0]
+
+
+def torch_alpha(pix_to_face, dists, sigma, dtype):
+    """SoftSilhouetteShader's K-plane branch: (H,W) alpha."""
+    return 1.0 - torch.prod(1.0 - torch.sigmoid(-dists.to(dtype) / sigma) * (pix_to_face >= 0), dim=-1)
+
+
+def route_with_grads(case, sigma, gamma, dtype, device, unit_bary=False):
+    """dict over NAMES: the torch route's output and its gradients to zbuf, bary, dists and face_attr under case['grad_out'].
+    With unit_bary the barycentrics carry no gradient (None)."""
+    leaves = {k: case[k].to(device).to(dtype).requires_grad_(True) for k in ("zbuf", "bary", "dists", "face_attr")}
+    planes = dict(pix_to_face=case["pix_to_face"].to(device), zbuf=leaves["zbuf"], bary=leaves["bary"], dists=leaves["dists"])
+    out = torch_route(planes, leaves["face_attr"], case["background"], sigma, gamma, dtype, unit_bary)
+    keys = [k for k in ("zbuf", "bary", "dists", "face_attr") if not (unit_bary and k == "bary")]
+    g = torch.autograd.grad(out, [leaves[k] for k in keys], case["grad_out"].to(device).to(dtype))
+    res = dict(out=out.detach(), grad_bary=None)
+    res.update({"grad_" + k: t for k, t in zip(keys, g)})
+    return res
+
+
+_CACHE = {}
+
+
+def referee_and_yardstick(key, case, sigma, gamma, device, unit_bary=False):
+    """(float64 referee, {name: yardstick}) of one case, computed once per (key, device)."""
+    ck = (key, sigma, gamma, str(device), unit_bary)
+    if ck not in _CACHE:
+        ref = route_with_grads(case, sigma, gamma, torch.float64, device, unit_bary)
+        f32 = route_with_grads(case, sigma, gamma, torch.float32, device, unit_bary)
+        yard = {n: relerr(f32[n], ref[n]) for n in NAMES if ref[n] is not None and float(ref[n].abs().max()) > 0}
+        _CACHE[ck] = (ref, yard)
+    return _CACHE[ck]
+
+
+def kat_zbuf_limit(case, gamma, znear=ZNEAR, zfar=ZFAR):
+    """K = 1 with delta clamped: the referee's z gradient is exactly 0 (the fragment's exponent is 0 whatever its depth); the
+    derivative's analytic size, through the clamped delta = 1e-10 alone."""
+    return (1e-10 / gamma) * float(case["grad_out"].abs().max()) * (float(case["face_attr"].abs().max()) + max(abs(x) for x in case["background"])) / (zfar - znear)
