@@ -147,7 +147,10 @@ def load_side(name, signatures):
             raise FohoError(f"{path} is version {ver()}, this binding is {version}: rebuild (make -C followmyhold_amd/csrc)")
         getattr(L, f"foho_{name}_last_error").restype = ctypes.c_char_p
         for fn, (restype, argtypes) in signatures.items():
-            f = getattr(L, fn)
+            try:
+                f = getattr(L, fn)
+            except AttributeError:      # an older library of the same version number: additive entry points are recognised by their symbol
+                raise FohoError(f"{path} does not export {fn}: rebuild (make -C followmyhold_amd/csrc)") from None
             f.restype, f.argtypes = restype, argtypes
         _sides[name] = L
     return L
@@ -175,12 +178,17 @@ RASTK_CULL_BACKFACES, RASTK_OVER_LIST = 1, 1
 RASTK_BLEND_MAX_D = 4    # FOHO_RASTK_BLEND_MAX_D
 RASTK_BLEND_UNIT_BARY, RASTK_BLEND_ALPHA_ONLY = 1, 2
 _RASTK_BLEND_HEAD = [vp, vp, vp, vp, vp, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f, vp, c_i]     # planes, face_attr, F H W K D, sigma gamma znear zfar, background, flags
+# verts_ndc, faces, V F H W K, blur_radius, raster_flags, face_attr, D, sigma gamma znear zfar, background, blend_flags
+_RASTK_RENDER_HEAD = [vp, vp, c_i, c_i, c_i, c_i, c_i, c_f, c_i, vp, c_i, c_f, c_f, c_f, c_f, vp, c_i]
 _RASTK_SIGNATURES = {
     "foho_rastk_blend_fwd": (ctypes.c_int, _RASTK_BLEND_HEAD + [vp, vp]),
     "foho_rastk_blend_bwd": (ctypes.c_int, _RASTK_BLEND_HEAD + [vp, vp, vp, vp, vp, vp]),
     "foho_rastk_workspace_bytes": (ctypes.c_size_t, [c_i, c_i, c_i, c_i, c_i, ctypes.c_int64]),
     "foho_rastk_fwd": (ctypes.c_int, [vp, vp, c_i, c_i, c_i, c_i, c_i, c_f, c_i, vp, vp, vp, vp, vp, vp, ctypes.c_int64, vp, ctypes.c_size_t, vp]),
-    "foho_rastk_bwd": (ctypes.c_int, [vp, vp, c_i, c_i, c_i, c_i, c_i, vp, vp, vp, vp, vp, c_f, vp])}
+    "foho_rastk_bwd": (ctypes.c_int, [vp, vp, c_i, c_i, c_i, c_i, c_i, vp, vp, vp, vp, vp, c_f, vp]),
+    # foho_rastk_render_*: _RASTK_RENDER_HEAD, then out, counts, overflow | grad_out, grad_verts_ndc, grad_face_attr, then list_cap, workspace, bytes, stream
+    "foho_rastk_render_fwd": (ctypes.c_int, _RASTK_RENDER_HEAD + [vp, vp, vp, ctypes.c_int64, vp, ctypes.c_size_t, vp]),
+    "foho_rastk_render_bwd": (ctypes.c_int, _RASTK_RENDER_HEAD + [vp, vp, vp, ctypes.c_int64, vp, ctypes.c_size_t, vp])}
 
 
 def rastk():

@@ -115,6 +115,32 @@ FOHO_RASTK_API int foho_rastk_blend_bwd(const int64_t* pix_to_face, const float*
                                         const float* grad_out, float* grad_zbuf, float* grad_bary, float* grad_dists,
                                         float* grad_face_attr, void* stream);
 
+/* foho_rastk_fwd and foho_rastk_blend_fwd in one: mesh -> blended image, without the (H,W,K) planes in memory.  The bins are
+ * foho_rastk_fwd's (the same workspace, foho_rastk_workspace_bytes, overflow and list_cap protocol: with FOHO_RASTK_OVER_LIST set no
+ * output was written and the workspace's first int64 holds the list_cap to call again with); the wave that selected and sorted a
+ * tile's K nearest keys then blends every pixel's column where it lies, in LDS.  out: (H,W,D+1) float32, or (H,W) with
+ * FOHO_RASTK_BLEND_ALPHA_ONLY; BITWISE what foho_rastk_blend_fwd gives on the planes of foho_rastk_fwd for the same arguments (one
+ * copy of the arithmetic, the same key order at the cut).  counts: int32 (H,W) as foho_rastk_fwd's, or NULL.  face_attr: (F,3,D), the
+ * F of the mesh; background: D floats in HOST memory (both may be NULL with FOHO_RASTK_BLEND_ALPHA_ONLY).  raster_flags:
+ * FOHO_RASTK_CULL_BACKFACES; blend_flags: FOHO_RASTK_BLEND_UNIT_BARY, FOHO_RASTK_BLEND_ALPHA_ONLY.  Memory: the workspace; nothing is
+ * proportional to K.  Asynchronous, no allocation, no host read.  The workspace must be kept, untouched, for foho_rastk_render_bwd.
+ * Refused with a negative status, never clamped: what foho_rastk_fwd and foho_rastk_blend_fwd refuse. */
+FOHO_RASTK_API int foho_rastk_render_fwd(const float* verts_ndc, const int32_t* faces, int32_t V, int32_t F, int32_t H, int32_t W, int32_t K,
+                                         float blur_radius, int32_t raster_flags, const float* face_attr, int32_t D, float sigma, float gamma,
+                                         float znear, float zfar, const float* background, int32_t blend_flags, float* out, int32_t* counts,
+                                         int32_t* overflow, int64_t list_cap, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The derivative of foho_rastk_render_fwd: grad_out (H,W,D+1), or (H,W) with FOHO_RASTK_BLEND_ALPHA_ONLY, -> grad_verts_ndc (V,3) and
+ * grad_face_attr (F,3,D), both ADDED to with float atomics; either may be NULL and its work is skipped (with
+ * FOHO_RASTK_BLEND_ALPHA_ONLY grad_face_attr is not touched).  Every other argument is the forward call's, and workspace is the one
+ * that call left: its tile lists are read, nothing is binned again.  The per-fragment gradients are foho_rastk_blend_bwd's and go
+ * straight into foho_rastk_bwd's per-fragment derivative; no plane-sized buffer exists. */
+FOHO_RASTK_API int foho_rastk_render_bwd(const float* verts_ndc, const int32_t* faces, int32_t V, int32_t F, int32_t H, int32_t W, int32_t K,
+                                         float blur_radius, int32_t raster_flags, const float* face_attr, int32_t D, float sigma, float gamma,
+                                         float znear, float zfar, const float* background, int32_t blend_flags, const float* grad_out,
+                                         float* grad_verts_ndc, float* grad_face_attr, int64_t list_cap, const void* workspace,
+                                         size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

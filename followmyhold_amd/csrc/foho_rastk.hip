@@ -12,6 +12,7 @@
 //                 sorts its column, re-evaluates the kept fragments from their keys and writes the planes
 //   k_rk_bwd      one thread per (pixel, k): foho_raster_bwd's derivative, float atomicAdd into the vertex gradient
 //   k_rk_blend_*  rastk_blend.inc: the consumer of the planes, shading and softmax blend with gradient, one thread per pixel
+//   k_rk_render_* rastk_render.inc: selection and blend in one kernel each way, mesh -> image -> vertex gradient without the planes
 // Compiled with foho_step.hip's flags (-ffp-contract=off, correctly rounded division and sqrt): the per-(pixel, face) arithmetic is
 // foho_common.h's eval_frag / clip_subtris / subtri_bary_to_face, the functions k_raster.inc's evaluate stage and k_raster_export
 // call, and that arithmetic decides face ids.
@@ -198,22 +199,15 @@ __device__ __forceinline__ bool eval_face(const float* fv, bool cull, float xf, 
     return eval_frag<false>(back0 ? t1 : t0, xf, yf, blur, sqrt_blur, out);
 }
 
-template <int KCAP>
-__global__ __launch_bounds__(64) void k_rk_select(const float* __restrict__ face_ndc, const unsigned* __restrict__ toff, const int* __restrict__ list,
-                                                  const Hdr* __restrict__ hdr, int H, int W, int K, PixAxis ax, PixAxis ay, float blur,
-                                                  float sqrt_blur, int cull, int tiles_x, int64_t* __restrict__ p2f, float* __restrict__ zbuf,
-                                                  float* __restrict__ bary, float* __restrict__ dists, int32_t* __restrict__ counts) {
-    __shared__ unsigned long long slab[KCAP * 64];
-    __shared__ float s_fv[CH * 9];
-    __shared__ int s_id[CH];
-    if (hdr->abort) return;
-    const int lane = threadIdx.x;
-    const int tile = blockIdx.x;
-    const int px = (tile % tiles_x) * TILE + (lane & (TILE - 1)), py = (tile / tiles_x) * TILE + (lane >> 3);
-    const bool in_img = px < W && py < H;
-    const float xf = pix_to_ndc(W - 1 - px, ax), yf = pix_to_ndc(H - 1 - py, ay);
-    const unsigned beg = toff[tile], end = toff[tile + 1];
-    int n = 0, cnt = 0, imax = 0;
+// The selection loop and the column sort of one wave's tile (k_rk_select, k_rk_render_fwd / _bwd): the tile's faces [beg, end) of
+// `list` stream through s_fv / s_id in chunks of CH, the lane keeps the K smallest keys of its pixel in its slab column
+// (slab[slot * 64 + lane]) and sorts them ascending.  Every lane of the wave calls it (it holds barriers); a lane outside the image
+// keeps nothing.  Returns the number of keys kept, cnt = the fragments the pixel received before the cut.
+__device__ __forceinline__ int select_sort(unsigned long long* slab, float* s_fv, int* s_id, const float* __restrict__ face_ndc,
+                                           const int* __restrict__ list, unsigned beg, unsigned end, int lane, bool in_img, int K, bool cull,
+                                           float xf, float yf, float blur, float sqrt_blur, int& cnt) {
+    int n = 0, imax = 0;
+    cnt = 0;
     unsigned long long kmax = 0ull;
     for (unsigned c0 = beg; c0 < end; c0 += CH) {
         const int m = (int)min((unsigned)CH, end - c0);
@@ -229,7 +223,7 @@ __global__ __launch_bounds__(64) void k_rk_select(const float* __restrict__ face
                 for (int k = 0; k < 9; k++) fv[k] = s_fv[j * 9 + k];
                 Frag fr;
                 int sub;
-                if (!eval_face(fv, cull != 0, xf, yf, blur, sqrt_blur, fr, sub)) continue;
+                if (!eval_face(fv, cull, xf, yf, blur, sqrt_blur, fr, sub)) continue;
                 // z >= 0 (pz < 0 leaves no fragment, -0 was canonicalised): the float's bits order as unsigned
                 const unsigned long long key = ((unsigned long long)__float_as_uint(fr.z) << 32) | ((unsigned)s_id[j] << 1) | (unsigned)(sub == 1);
                 cnt++;
@@ -255,7 +249,6 @@ __global__ __launch_bounds__(64) void k_rk_select(const float* __restrict__ face
         }
         __syncthreads();
     }
-    if (!in_img) return;
     // the lane's column, ascending (insertion sort: columns are short, and nearly always far below K)
     for (int i = 1; i < n; i++) {
         const unsigned long long v = slab[i * 64 + lane];
@@ -268,6 +261,43 @@ __global__ __launch_bounds__(64) void k_rk_select(const float* __restrict__ face
         }
         slab[j * 64 + lane] = v;
     }
+    return n;
+}
+
+// the fragment a kept key came from, evaluated again: its face id; fr.z is bitwise the key's high word.  BARY: b = its barycentrics,
+// which refer to the UNCLIPPED face, like pytorch3d's
+template <bool BARY>
+__device__ __forceinline__ int eval_kept(unsigned long long key, const float* __restrict__ face_ndc, bool cull, float xf, float yf, float blur,
+                                         float sqrt_blur, Frag& fr, float* b) {
+    const int f = (int)((unsigned)(key & 0xffffffffull) >> 1);
+    float fv[9];
+    for (int q = 0; q < 9; q++) fv[q] = face_ndc[9 * (size_t)f + q];
+    int sub;
+    eval_face(fv, cull, xf, yf, blur, sqrt_blur, fr, sub);
+    if (BARY) {
+        b[0] = fr.c0, b[1] = fr.c1, b[2] = fr.c2;
+        if (sub >= 0) subtri_bary_to_face(fv, Z_CLIP, sub, b);
+    }
+    return f;
+}
+
+template <int KCAP>
+__global__ __launch_bounds__(64) void k_rk_select(const float* __restrict__ face_ndc, const unsigned* __restrict__ toff, const int* __restrict__ list,
+                                                  const Hdr* __restrict__ hdr, int H, int W, int K, PixAxis ax, PixAxis ay, float blur,
+                                                  float sqrt_blur, int cull, int tiles_x, int64_t* __restrict__ p2f, float* __restrict__ zbuf,
+                                                  float* __restrict__ bary, float* __restrict__ dists, int32_t* __restrict__ counts) {
+    __shared__ unsigned long long slab[KCAP * 64];
+    __shared__ float s_fv[CH * 9];
+    __shared__ int s_id[CH];
+    if (hdr->abort) return;
+    const int lane = threadIdx.x;
+    const int tile = blockIdx.x;
+    const int px = (tile % tiles_x) * TILE + (lane & (TILE - 1)), py = (tile / tiles_x) * TILE + (lane >> 3);
+    const bool in_img = px < W && py < H;
+    const float xf = pix_to_ndc(W - 1 - px, ax), yf = pix_to_ndc(H - 1 - py, ay);
+    int cnt;
+    const int n = select_sort(slab, s_fv, s_id, face_ndc, list, toff[tile], toff[tile + 1], lane, in_img, K, cull != 0, xf, yf, blur, sqrt_blur, cnt);
+    if (!in_img) return;
     const size_t pix = (size_t)py * W + px;
     if (counts) counts[pix] = cnt;
     for (int k = 0; k < K; k++) {
@@ -275,16 +305,8 @@ __global__ __launch_bounds__(64) void k_rk_select(const float* __restrict__ face
         int64_t face = -1;
         float z = -1.0f, sd = -1.0f, b[3] = {-1.0f, -1.0f, -1.0f};
         if (k < n) {
-            const unsigned id = (unsigned)(slab[k * 64 + lane] & 0xffffffffull);
-            const int f = (int)(id >> 1);
-            float fv[9];
-            for (int q = 0; q < 9; q++) fv[q] = face_ndc[9 * (size_t)f + q];
             Frag fr;
-            int sub;
-            eval_face(fv, cull != 0, xf, yf, blur, sqrt_blur, fr, sub);  // the fragment the key came from
-            b[0] = fr.c0, b[1] = fr.c1, b[2] = fr.c2;
-            if (sub >= 0) subtri_bary_to_face(fv, Z_CLIP, sub, b);  // barycentrics refer to the UNCLIPPED face, like pytorch3d's
-            face = f;
+            face = eval_kept<true>(slab[k * 64 + lane], face_ndc, cull != 0, xf, yf, blur, sqrt_blur, fr, b);
             z = fr.z;
             sd = fr.sdist;
         }
@@ -322,6 +344,17 @@ __global__ __launch_bounds__(TPB) void k_rk_bwd(const float* __restrict__ verts,
             if (gv[3 * k + q] != 0.f) atomicAdd(&g_verts[3 * (size_t)vi[k] + q], gv[3 * k + q]);
 }
 
+// setup, scan and fill: the tile lists of one frame into the workspace (foho_rastk_fwd, foho_rastk_render_fwd); false: the memset failed
+bool bin_faces(const Ws& w, const float* verts_ndc, const int32_t* faces, int V, int F, const PixAxis& ax, const PixAxis& ay, float sqrt_blur,
+               int64_t list_cap, int32_t* overflow, hipStream_t st) {
+    if (hipMemsetAsync(w.tcount, 0, w.tiles * 4, st) != hipSuccess) return false;
+    hipLaunchKernelGGL(k_rk_setup, dim3(blocks_for(F, TPB)), dim3(TPB), 0, st, verts_ndc, faces, V, F, ax, ay, sqrt_blur, w.tiles_x, w.face_ndc,
+                       w.tbox, w.tcount);
+    hipLaunchKernelGGL(k_rk_scan, dim3(1), dim3(TPB), 0, st, w.tcount, w.toff, w.cursor, (long long)w.tiles, (long long)list_cap, w.hdr, overflow);
+    hipLaunchKernelGGL(k_rk_fill, dim3(blocks_for(F, TPB)), dim3(TPB), 0, st, w.tbox, F, w.tiles_x, w.cursor, w.list, w.hdr);
+    return true;
+}
+
 bool dims_ok(int32_t V, int32_t F, int32_t H, int32_t W) {
     return V >= 1 && F >= 1 && F <= (1 << 30) && H >= 1 && W >= 1 && H <= 8192 && W <= 8192 && (size_t)H * W <= ((size_t)1 << 25);
 }
@@ -355,11 +388,7 @@ FOHO_RASTK_API int foho_rastk_fwd(const float* verts_ndc, const int32_t* faces, 
     const PixAxis ax = pix_axis(W, H), ay = pix_axis(H, W);
     const float sqrt_blur = sqrtf(blur_radius);
     const int cull = (flags & FOHO_RASTK_CULL_BACKFACES) ? 1 : 0;
-    if (hipMemsetAsync(w.tcount, 0, w.tiles * 4, st) != hipSuccess) return fail(-2, "foho_rastk_fwd: memset failed");
-    hipLaunchKernelGGL(k_rk_setup, dim3(blocks_for(F, TPB)), dim3(TPB), 0, st, verts_ndc, faces, V, F, ax, ay, sqrt_blur, w.tiles_x, w.face_ndc,
-                       w.tbox, w.tcount);
-    hipLaunchKernelGGL(k_rk_scan, dim3(1), dim3(TPB), 0, st, w.tcount, w.toff, w.cursor, (long long)w.tiles, (long long)list_cap, w.hdr, overflow);
-    hipLaunchKernelGGL(k_rk_fill, dim3(blocks_for(F, TPB)), dim3(TPB), 0, st, w.tbox, F, w.tiles_x, w.cursor, w.list, w.hdr);
+    if (!bin_faces(w, verts_ndc, faces, V, F, ax, ay, sqrt_blur, list_cap, overflow, st)) return fail(-2, "foho_rastk_fwd: memset failed");
 #define RK_SELECT(KCAP)                                                                                                                  \
     hipLaunchKernelGGL(k_rk_select<KCAP>, dim3((unsigned)w.tiles), dim3(64), 0, st, w.face_ndc, w.toff, w.list, w.hdr, H, W, K, ax, ay, \
                        blur_radius, sqrt_blur, cull, w.tiles_x, pix_to_face, zbuf, bary, dists, counts)
@@ -385,4 +414,5 @@ FOHO_RASTK_API int foho_rastk_bwd(const float* verts_ndc, const int32_t* faces, 
 
 }  // extern "C"
 
-#include "rastk_blend.inc"  // foho_rastk_blend_fwd / _bwd
+#include "rastk_blend.inc"   // foho_rastk_blend_fwd / _bwd
+#include "rastk_render.inc"  // foho_rastk_render_fwd / _bwd

@@ -2,7 +2,8 @@
 // foho_rastk_fwd writes, one launch each way.  Included by foho_rastk.hip behind its entry points (fail / launched / blocks_for / TPB
 // are foho_side.h's).  DESIGN.md section 3C.
 //
-// One thread per pixel, no LDS, no workspace.  The planes are front-packed: a pixel's fragments are its n leading entries with an id
+// One thread per pixel, no LDS, no workspace.  The sweeps are templates over where a pixel's fragments come from and where their
+// gradients go, so that rastk_render.inc runs the same arithmetic on the keys k_rk_select keeps in LDS.  The planes are front-packed: a pixel's fragments are its n leading entries with an id
 // in 0 .. F-1, and every sweep stops at n, so a pixel costs what it holds, not K.  Nothing K-sized lives in registers: what a later
 // sweep needs of an earlier one it recomputes from the planes.
 //   forward   sweep A: n, max_k zinv_k and its first index; sweep B: p, q = 1 - p, w, the sums S = sum w, num_c = sum w c_kc, the
@@ -64,17 +65,42 @@ struct PixSums {
 
 __device__ __forceinline__ float zinv_of(float z, const BlendCfg& c) { return (c.zfar - z) / c.zrange; }
 
-// sweeps A and B of one pixel (id, z, d: the pixel's K entries; b: its 3 K barycentrics)
-template <int D, bool UNIT>
-__device__ __forceinline__ PixSums<D> pixel_sums(const int64_t* __restrict__ id, const float* __restrict__ z, const float* __restrict__ b,
-                                                 const float* __restrict__ d, const float* __restrict__ attr, const BlendCfg& c) {
+// A pixel's fragments as the sweeps see them -- has(k): k is one of them (they are the leading k); z(k), face(k); shade<BARY>(k, d, b):
+// the distance and, with BARY, the three barycentrics.  PlaneFrags reads the K planes; SlabFrags (rastk_render.inc) the sorted keys of
+// k_rk_select's slab.  The sweeps below are the one copy of the blend's arithmetic for both.
+struct PlaneFrags {
+    const int64_t* id;
+    const float *zb, *ba, *di;
+    int K;
+    int64_t lim;  // ids outside 0 .. lim-1 end the pixel's fragments
+    __device__ __forceinline__ bool has(int k) const { return k < K && id[k] >= 0 && id[k] < lim; }
+    __device__ __forceinline__ float z(int k) const { return zb[k]; }
+    __device__ __forceinline__ int64_t face(int k) const { return id[k]; }
+    template <bool BARY>
+    __device__ __forceinline__ void shade(int k, float& d, float* b) const {
+        d = di[k];
+        if (BARY) b[0] = ba[3 * k], b[1] = ba[3 * k + 1], b[2] = ba[3 * k + 2];
+    }
+};
+
+// where sweep C's per-fragment gradients go: PlaneSink writes them into the plane gradients (each may be NULL)
+struct PlaneSink {
+    float *g_z, *g_b, *g_d;
+    __device__ __forceinline__ void emit(int k, int64_t, float gz, const float* gb, float gd) const {
+        if (g_z) g_z[k] = gz;
+        if (g_d) g_d[k] = gd;
+        if (g_b) g_b[3 * k] = gb[0], g_b[3 * k + 1] = gb[1], g_b[3 * k + 2] = gb[2];
+    }
+};
+
+// sweeps A and B of one pixel
+template <int D, bool UNIT, class FRAGS>
+__device__ __forceinline__ PixSums<D> pixel_sums(const FRAGS& fr, const float* __restrict__ attr, const BlendCfg& c) {
     PixSums<D> s;
     s.n = 0, s.amax = 0;
     float zmax = 0.0f;
-    for (int k = 0; k < c.K; k++) {
-        const int64_t f = id[k];
-        if (f < 0 || f >= c.F) break;
-        const float zi = zinv_of(z[k], c);
+    for (int k = 0; fr.has(k); k++) {
+        const float zi = zinv_of(fr.z(k), c);
         if (k == 0 || zi > zmax) zmax = zi, s.amax = k;
         s.n = k + 1;
     }
@@ -87,16 +113,110 @@ __device__ __forceinline__ PixSums<D> pixel_sums(const int64_t* __restrict__ id,
     for (int ch = 0; ch < D; ch++) s.num[ch] = 0.0f;
     s.q.pnz = 1.0f, s.q.nzero = 0;
     for (int k = 0; k < s.n; k++) {
-        float p, q, col[D];
-        sigmoid_pq(d[k], c.sigma, p, q);
+        float p, q, col[D], d, b[3];
+        fr.template shade<!UNIT>(k, d, b);
+        sigmoid_pq(d, c.sigma, p, q);
         s.q.mul(q);
-        const float w = p * expf((zinv_of(z[k], c) - s.m) / c.gamma);
-        frag_colour<D, UNIT>(attr + (size_t)id[k] * 3 * D, UNIT ? nullptr : b + 3 * k, col);
+        const float w = p * expf((zinv_of(fr.z(k), c) - s.m) / c.gamma);
+        frag_colour<D, UNIT>(attr + (size_t)fr.face(k) * 3 * D, b, col);
         s.S += w;
 #pragma unroll
         for (int ch = 0; ch < D; ch++) s.num[ch] += w * col[ch];
     }
     return s;
+}
+
+// the pixel of the image from its sums: the D blended channels, then alpha
+template <int D>
+__device__ __forceinline__ void write_pixel(const PixSums<D>& s, const BlendCfg& c, float* po) {
+    const float den = s.S + s.delta;
+#pragma unroll
+    for (int ch = 0; ch < D; ch++) po[ch] = (s.num[ch] + s.delta * c.bg[ch]) / den;  // no fragment: (0 + 1 bg) / 1
+    po[D] = 1.0f - s.q.full();
+}
+
+// sweep C of one pixel with fragments: the gradients of fragment k from the pixel's sums, to the sink (g_bary is 0 with UNIT), and the
+// attribute gradient by float atomicAdd (g_attr may be NULL).  go: the pixel's D + 1 entries of grad_out.
+template <int D, bool UNIT, class FRAGS, class SINK>
+__device__ __forceinline__ void pixel_grads(const FRAGS& fr, const PixSums<D>& s, const float* __restrict__ attr, const BlendCfg& c,
+                                            const float* __restrict__ go, const SINK& sink, float* g_attr) {
+    const float den = s.S + s.delta;
+    // rgb_c = (num_c + delta bg_c) / den: gn_c = dL/dnum_c; dL/dw_k = sum_c gn_c (c_kc - rgb_c); dL/ddelta = sum_c gn_c (bg_c - rgb_c)
+    float gn[D], rgb[D], g_delta = 0.0f;
+#pragma unroll
+    for (int ch = 0; ch < D; ch++) {
+        rgb[ch] = (s.num[ch] + s.delta * c.bg[ch]) / den;
+        gn[ch] = go[ch] / den;
+        g_delta += gn[ch] * (c.bg[ch] - rgb[ch]);
+    }
+    const float g_alpha = go[D];  // out alpha = 1 - prod q: d alpha / d p_k = prod_{j != k} q_j
+    // m enters every exponent and, where delta is not clamped, delta.  With u_k = dL/d(zinv_k - m) = dL/dw_k w_k / gamma the max's
+    // gradient is -(sum_k u_k + v), v = dL/ddelta delta / gamma where delta is not clamped and 0 where it is, and torch sends it to
+    // fragment amax, whose own u cancels: it receives -(sum_{k != amax} u_k + v), summed WITHOUT that term.  So a pixel's only
+    // fragment gets exactly -v (0 where delta is clamped, as in torch), and the nearest fragment, whose colour rgb is closest to,
+    // never takes its gradient from the cancelling difference c_k - rgb.  Where delta is not clamped the sum equals u_amax (rgb is
+    // homogeneous of degree 0 in (w, delta): m cancels).  The sum is compensated (Kahan): K - 1 terms of one size leave one of them.
+    // Fragment amax's gradients therefore leave last, when the sum is complete: its g_dist and g_bary wait in registers.
+    float u_others = s.m_passes && s.draw >= BLEND_EPS ? g_delta * s.draw / c.gamma : 0.0f, u_comp = 0.0f;
+    float held_d = 0.0f, held_b[3] = {0.0f, 0.0f, 0.0f};
+    for (int k = 0; k < s.n; k++) {
+        float p, q, col[D], d, bw[3] = {1.0f, 1.0f, 1.0f}, gb[3] = {0.0f, 0.0f, 0.0f};
+        fr.template shade<!UNIT>(k, d, bw);
+        sigmoid_pq(d, c.sigma, p, q);
+        const float e = expf((zinv_of(fr.z(k), c) - s.m) / c.gamma), w = p * e;
+        const int64_t f = fr.face(k);
+        const float* fa = attr + (size_t)f * 3 * D;
+        frag_colour<D, UNIT>(fa, bw, col);
+        float g_w = 0.0f;
+#pragma unroll
+        for (int ch = 0; ch < D; ch++) g_w += gn[ch] * (col[ch] - rgb[ch]);
+        const float u = g_w * w / c.gamma;
+        const bool hold = k == s.amax && s.m_passes;
+        if (!hold) {
+            const float y = u - u_comp, t = u_others + y;
+            u_comp = (t - u_others) - y;
+            u_others = t;
+        }
+        const float gd = -((g_alpha * s.q.without(q) + g_w * e) * (p * q)) / c.sigma;
+#pragma unroll
+        for (int ch = 0; ch < D; ch++) {
+            const float g_c = gn[ch] * w;  // dL/dc_kc
+#pragma unroll
+            for (int j = 0; j < 3; j++) {
+                gb[j] += g_c * fa[j * D + ch];
+                const float ga = bw[j] * g_c;
+                if (g_attr && ga != 0.0f) atomicAdd(&g_attr[(size_t)f * 3 * D + j * D + ch], ga);
+            }
+        }
+        if (UNIT) gb[0] = gb[1] = gb[2] = 0.0f;  // the weights are constants
+        if (hold) held_d = gd, held_b[0] = gb[0], held_b[1] = gb[1], held_b[2] = gb[2];
+        else sink.emit(k, f, -u / c.zrange, gb, gd);  // zinv = (zfar - z) / zrange
+    }
+    if (s.m_passes) sink.emit(s.amax, fr.face(s.amax), u_others / c.zrange, held_b, held_d);
+}
+
+// FOHO_RASTK_BLEND_ALPHA_ONLY: alpha = 1 - prod_k q_k from the distances alone.  The product; returns the pixel's fragments
+template <class FRAGS>
+__device__ __forceinline__ int alpha_prod(const FRAGS& fr, float sigma, QProd& pr) {
+    pr.pnz = 1.0f, pr.nzero = 0;
+    int n = 0;
+    for (; fr.has(n); n++) {
+        float p, q, d;
+        fr.template shade<false>(n, d, nullptr);
+        sigmoid_pq(d, sigma, p, q);
+        pr.mul(q);
+    }
+    return n;
+}
+template <class FRAGS, class SINK>
+__device__ __forceinline__ void alpha_grads(const FRAGS& fr, int n, const QProd& pr, float sigma, float g_alpha, const SINK& sink) {
+    const float none[3] = {0.0f, 0.0f, 0.0f};
+    for (int k = 0; k < n; k++) {
+        float p, q, d;
+        fr.template shade<false>(k, d, nullptr);
+        sigmoid_pq(d, sigma, p, q);
+        sink.emit(k, fr.face(k), 0.0f, none, -((g_alpha * pr.without(q)) * (p * q)) / sigma);
+    }
 }
 
 template <int D, bool UNIT>
@@ -106,12 +226,8 @@ __global__ __launch_bounds__(TPB) void k_rk_blend_fwd(const int64_t* __restrict_
     const size_t pix = (size_t)blockIdx.x * TPB + threadIdx.x;
     if (pix >= c.pixels) return;
     const size_t o = pix * (size_t)c.K;
-    const PixSums<D> s = pixel_sums<D, UNIT>(p2f + o, zbuf + o, UNIT ? nullptr : bary + 3 * o, dists + o, attr, c);
-    float* po = out + pix * (D + 1);
-    const float den = s.S + s.delta;
-#pragma unroll
-    for (int ch = 0; ch < D; ch++) po[ch] = (s.num[ch] + s.delta * c.bg[ch]) / den;  // no fragment: (0 + 1 bg) / 1
-    po[D] = 1.0f - s.q.full();
+    const PlaneFrags fr = {p2f + o, zbuf + o, UNIT ? nullptr : bary + 3 * o, dists + o, c.K, c.F};
+    write_pixel<D>(pixel_sums<D, UNIT>(fr, attr, c), c, out + pix * (D + 1));
 }
 
 template <int D, bool UNIT>
@@ -122,72 +238,20 @@ __global__ __launch_bounds__(TPB) void k_rk_blend_bwd(const int64_t* __restrict_
     const size_t pix = (size_t)blockIdx.x * TPB + threadIdx.x;
     if (pix >= c.pixels) return;
     const size_t o = pix * (size_t)c.K;
-    const int64_t* id = p2f + o;
-    if (id[0] < 0 || id[0] >= c.F) return;  // no fragment: nothing depends on the planes
-    const float *z = zbuf + o, *d = dists + o, *b = UNIT ? nullptr : bary + 3 * o;
-    const PixSums<D> s = pixel_sums<D, UNIT>(id, z, b, d, attr, c);
-    const float den = s.S + s.delta;
-    // rgb_c = (num_c + delta bg_c) / den: gn_c = dL/dnum_c; dL/dw_k = sum_c gn_c (c_kc - rgb_c); dL/ddelta = sum_c gn_c (bg_c - rgb_c)
-    float gn[D], rgb[D], g_delta = 0.0f;
-#pragma unroll
-    for (int ch = 0; ch < D; ch++) {
-        rgb[ch] = (s.num[ch] + s.delta * c.bg[ch]) / den;
-        gn[ch] = g_out[pix * (D + 1) + ch] / den;
-        g_delta += gn[ch] * (c.bg[ch] - rgb[ch]);
-    }
-    const float g_alpha = g_out[pix * (D + 1) + D];  // out alpha = 1 - prod q: d alpha / d p_k = prod_{j != k} q_j
-    // m enters every exponent and, where delta is not clamped, delta.  With u_k = dL/d(zinv_k - m) = dL/dw_k w_k / gamma the max's
-    // gradient is -(sum_k u_k + v), v = dL/ddelta delta / gamma where delta is not clamped and 0 where it is, and torch sends it to
-    // fragment amax, whose own u cancels: it receives -(sum_{k != amax} u_k + v), summed WITHOUT that term.  So a pixel's only
-    // fragment gets exactly -v (0 where delta is clamped, as in torch), and the nearest fragment, whose colour rgb is closest to,
-    // never takes its gradient from the cancelling difference c_k - rgb.  Where delta is not clamped the sum equals u_amax (rgb is
-    // homogeneous of degree 0 in (w, delta): m cancels).  The sum is compensated (Kahan): K - 1 terms of one size leave one of them.
-    float u_others = s.m_passes && s.draw >= BLEND_EPS ? g_delta * s.draw / c.gamma : 0.0f, u_comp = 0.0f;
-    for (int k = 0; k < s.n; k++) {
-        float p, q, col[D];
-        sigmoid_pq(d[k], c.sigma, p, q);
-        const float e = expf((zinv_of(z[k], c) - s.m) / c.gamma), w = p * e;
-        const float* fa = attr + (size_t)id[k] * 3 * D;
-        frag_colour<D, UNIT>(fa, b ? b + 3 * k : nullptr, col);
-        float g_w = 0.0f;
-#pragma unroll
-        for (int ch = 0; ch < D; ch++) g_w += gn[ch] * (col[ch] - rgb[ch]);
-        const float u = g_w * w / c.gamma;
-        if (k != s.amax || !s.m_passes) {
-            if (g_z) g_z[o + k] = -u / c.zrange;  // zinv = (zfar - z) / zrange
-            const float y = u - u_comp, t = u_others + y;
-            u_comp = (t - u_others) - y;
-            u_others = t;
-        }
-        if (g_d) g_d[o + k] = -((g_alpha * s.q.without(q) + g_w * e) * (p * q)) / c.sigma;
-        float bw[3] = {1.0f, 1.0f, 1.0f}, gb[3] = {0.0f, 0.0f, 0.0f};
-        if (!UNIT) bw[0] = b[3 * k], bw[1] = b[3 * k + 1], bw[2] = b[3 * k + 2];
-#pragma unroll
-        for (int ch = 0; ch < D; ch++) {
-            const float g_c = gn[ch] * w;  // dL/dc_kc
-#pragma unroll
-            for (int j = 0; j < 3; j++) {
-                gb[j] += g_c * fa[j * D + ch];
-                const float ga = bw[j] * g_c;
-                if (g_attr && ga != 0.0f) atomicAdd(&g_attr[(size_t)id[k] * 3 * D + j * D + ch], ga);
-            }
-        }
-        if (!UNIT && g_b) g_b[3 * (o + k)] = gb[0], g_b[3 * (o + k) + 1] = gb[1], g_b[3 * (o + k) + 2] = gb[2];
-    }
-    if (s.m_passes && g_z) g_z[o + s.amax] = u_others / c.zrange;
+    const PlaneFrags fr = {p2f + o, zbuf + o, UNIT ? nullptr : bary + 3 * o, dists + o, c.K, c.F};
+    if (!fr.has(0)) return;  // no fragment: nothing depends on the planes
+    const PlaneSink sink = {g_z ? g_z + o : nullptr, !UNIT && g_b ? g_b + 3 * o : nullptr, g_d ? g_d + o : nullptr};
+    pixel_grads<D, UNIT>(fr, pixel_sums<D, UNIT>(fr, attr, c), attr, c, g_out + pix * (D + 1), sink, g_attr);
 }
 
-// FOHO_RASTK_BLEND_ALPHA_ONLY: out (H,W) = 1 - prod_k q_k; only the ids and the distances are read
+// FOHO_RASTK_BLEND_ALPHA_ONLY: out (H,W) = 1 - prod_k q_k; only the ids and the distances are read, and a negative id alone ends a pixel
 __global__ __launch_bounds__(TPB) void k_rk_alpha_fwd(const int64_t* __restrict__ p2f, const float* __restrict__ dists, BlendCfg c, float* __restrict__ out) {
     const size_t pix = (size_t)blockIdx.x * TPB + threadIdx.x;
     if (pix >= c.pixels) return;
     const size_t o = pix * (size_t)c.K;
-    QProd pr = {1.0f, 0};
-    for (int k = 0; k < c.K && p2f[o + k] >= 0; k++) {
-        float p, q;
-        sigmoid_pq(dists[o + k], c.sigma, p, q);
-        pr.mul(q);
-    }
+    const PlaneFrags fr = {p2f + o, nullptr, nullptr, dists + o, c.K, INT64_MAX};
+    QProd pr;
+    alpha_prod(fr, c.sigma, pr);
     out[pix] = 1.0f - pr.full();
 }
 
@@ -196,38 +260,43 @@ __global__ __launch_bounds__(TPB) void k_rk_alpha_bwd(const int64_t* __restrict_
     const size_t pix = (size_t)blockIdx.x * TPB + threadIdx.x;
     if (pix >= c.pixels) return;
     const size_t o = pix * (size_t)c.K;
-    QProd pr = {1.0f, 0};
-    int n = 0;
-    for (; n < c.K && p2f[o + n] >= 0; n++) {
-        float p, q;
-        sigmoid_pq(dists[o + n], c.sigma, p, q);
-        pr.mul(q);
-    }
-    const float g_alpha = g_out[pix];
-    for (int k = 0; k < n; k++) {
-        float p, q;
-        sigmoid_pq(dists[o + k], c.sigma, p, q);
-        g_d[o + k] = -((g_alpha * pr.without(q)) * (p * q)) / c.sigma;
-    }
+    const PlaneFrags fr = {p2f + o, nullptr, nullptr, dists + o, c.K, INT64_MAX};
+    QProd pr;
+    const int n = alpha_prod(fr, c.sigma, pr);
+    const PlaneSink sink = {nullptr, nullptr, g_d + o};
+    alpha_grads(fr, n, pr, c.sigma, g_out[pix], sink);
 }
 
 // the checks both entry points share; 0 or the refusal's status
-int blend_args(const char* fn, const int64_t* p2f, const float* zbuf, const float* bary, const float* dists, const float* attr, int32_t F,
-               int32_t H, int32_t W, int32_t K, int32_t D, float sigma, float gamma, float znear, float zfar, const float* background,
-               int32_t flags, BlendCfg& c) {
-    const std::string who = std::string(fn) + ": ";
+// ... the part of them that needs no plane: flags, K, D, the frame, the scalars (foho_rastk_render_* checks these too)
+int blend_scalars(const std::string& who, int32_t F, int32_t H, int32_t W, int32_t K, int32_t D, float sigma, float gamma, float znear, float zfar,
+                  int32_t flags) {
     if (flags & ~(FOHO_RASTK_BLEND_UNIT_BARY | FOHO_RASTK_BLEND_ALPHA_ONLY)) return fail(-1, who + "unknown flag");
-    const bool alpha = flags & FOHO_RASTK_BLEND_ALPHA_ONLY, unit = flags & FOHO_RASTK_BLEND_UNIT_BARY;
+    const bool alpha = flags & FOHO_RASTK_BLEND_ALPHA_ONLY;
     if (!k_ok(K)) return fail(-1, who + "K outside 1 .. 128");
     if (D < 1 || D > FOHO_RASTK_BLEND_MAX_D) return fail(-1, who + "D outside 1 .. 4");
     if (!dims_ok(1, alpha ? 1 : F, H, W)) return fail(-1, who + "F, H or W out of range");
     if (!(sigma > 0.0f)) return fail(-1, who + "sigma must be positive");
     if (!alpha && !(gamma > 0.0f)) return fail(-1, who + "gamma must be positive");
     if (!alpha && !(zfar > znear)) return fail(-1, who + "zfar must exceed znear");
-    if (!p2f || !dists || (!alpha && (!zbuf || !attr || !background || (!unit && !bary)))) return fail(-1, who + "null argument");
+    return 0;
+}
+void blend_cfg(BlendCfg& c, int32_t F, int32_t H, int32_t W, int32_t K, int32_t D, float sigma, float gamma, float znear, float zfar,
+               const float* background, int32_t flags) {
+    const bool alpha = flags & FOHO_RASTK_BLEND_ALPHA_ONLY;
     c.sigma = sigma, c.gamma = gamma, c.zfar = zfar, c.zrange = zfar - znear;
     for (int ch = 0; ch < 4; ch++) c.bg[ch] = (!alpha && ch < D) ? background[ch] : 0.0f;
     c.K = K, c.F = F, c.pixels = (size_t)H * W;
+}
+int blend_args(const char* fn, const int64_t* p2f, const float* zbuf, const float* bary, const float* dists, const float* attr, int32_t F,
+               int32_t H, int32_t W, int32_t K, int32_t D, float sigma, float gamma, float znear, float zfar, const float* background,
+               int32_t flags, BlendCfg& c) {
+    const std::string who = std::string(fn) + ": ";
+    const int bad = blend_scalars(who, F, H, W, K, D, sigma, gamma, znear, zfar, flags);
+    if (bad) return bad;
+    const bool alpha = flags & FOHO_RASTK_BLEND_ALPHA_ONLY, unit = flags & FOHO_RASTK_BLEND_UNIT_BARY;
+    if (!p2f || !dists || (!alpha && (!zbuf || !attr || !background || (!unit && !bary)))) return fail(-1, who + "null argument");
+    blend_cfg(c, F, H, W, K, D, sigma, gamma, znear, zfar, background, flags);
     return 0;
 }
 

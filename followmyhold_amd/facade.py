@@ -8,7 +8,8 @@ The reference's patched pipeline talks to its geometry libraries through a small
 batch size, guid_config.py:9).  Rasterisation, nearest neighbours and the SDF pieces are HIP operators behind
 torch.autograd.Functions; the glue the reference itself writes in torch (shader blend, normalisation) stays in
 torch ops on the device -- unless BlendParams(fused=True) sends K-fragment planes through ops.blend_k / blend_k_alpha (one launch
-each way).  For throughput use followmyhold_amd.engine.GuidanceBatch (the fused step) instead.
+each way), or MeshRenderer(fused_render=True) / render_mesh render the mesh in one operator without the planes
+(ops.render_k).  For throughput use followmyhold_amd.engine.GuidanceBatch (the fused step) instead.
 
 The K=100 silhouette alpha is differentiable (foho_raster_sil_bwd: through every fragment of the pixels with fractional
 coverage); its sigma comes from the shader's blend_params.
@@ -305,14 +306,65 @@ class SoftSilhouetteShader(ShaderBase):
         return torch.cat([rgb, a[..., None]], dim=-1)
 
 
+def _render_inputs(meshes, cameras, raster_settings, blend_params):
+    """What the fused render takes from the facade's objects; refuses settings it does not serve."""
+    if not getattr(raster_settings, "k_fragments", False):
+        raise ValueError("the fused render needs RasterizationSettings(k_fragments=True)")
+    if not getattr(blend_params, "fused", False):
+        raise ValueError("the fused render needs BlendParams(fused=True)")
+    H, W = raster_settings.image_size
+    ndc = cameras.transform_points_ndc(meshes.verts_packed())
+    return ndc, meshes.faces_packed().contiguous(), H, W, raster_settings.faces_per_pixel, raster_settings.blur_radius
+
+
+def render_mesh(meshes, cameras, raster_settings, face_attributes, blend_params):
+    """MeshRasterizer(cameras, raster_settings)(meshes) + blend_fragments(.., face_attributes, blend_params, cameras.znear, cameras.zfar)
+    as one ops.render_k call: (1, H, W, D+1), bitwise the same image, without the (H,W,K) planes in memory.  Needs
+    RasterizationSettings(k_fragments=True) and BlendParams(fused=True); face_attributes (F,3,D) float32, 1 <= D <= 4."""
+    ndc, faces, H, W, K, blur = _render_inputs(meshes, cameras, raster_settings, blend_params)
+    return ops.render_k(ndc, faces, H, W, K, blur, face_attributes, blend_params.sigma, blend_params.gamma, cameras.znear, cameras.zfar,
+                        blend_params.background_color, cull_backfaces=raster_settings.cull_backfaces)[None]
+
+
 class MeshRenderer:
-    def __init__(self, rasterizer, shader):
-        self.rasterizer, self.shader = rasterizer, shader
+    def __init__(self, rasterizer, shader, fused_render=False):
+        # fused_render=True: rasteriser and shader run as ONE operator, ops.render_k / render_k_alpha (mesh -> image, no (H,W,K) planes in
+        # memory; DESIGN 3D).  Needs RasterizationSettings(k_fragments=True), BlendParams(fused=True) and a PhongNormalShader or a
+        # SoftSilhouetteShader.  False (default): rasterizer, then shader, on whatever route their settings choose.
+        self.rasterizer, self.shader, self.fused_render = rasterizer, shader, bool(fused_render)
+        if self.fused_render:
+            self._check_fused(getattr(shader, "blend_params", None))
+
+    def _check_fused(self, blend_params):
+        if type(self.shader) not in (PhongNormalShader, SoftSilhouetteShader):
+            raise ValueError("MeshRenderer(fused_render=True) serves PhongNormalShader and SoftSilhouetteShader only")
+        if not getattr(self.rasterizer.raster_settings, "k_fragments", False):
+            raise ValueError("MeshRenderer(fused_render=True) needs RasterizationSettings(k_fragments=True)")
+        if not getattr(blend_params, "fused", False):
+            raise ValueError("MeshRenderer(fused_render=True) needs BlendParams(fused=True)")
 
     def to(self, device):
         return self
 
+    def _render_fused(self, meshes, **kwargs):
+        cameras = kwargs.get("cameras", self.shader.cameras if self.shader.cameras is not None else self.rasterizer.cameras)
+        bp = kwargs.get("blend_params", self.shader.blend_params)
+        self._check_fused(bp)
+        rs = self.rasterizer.raster_settings
+        ndc, faces, H, W, K, blur = _render_inputs(meshes, kwargs.get("cameras", self.rasterizer.cameras), rs, bp)
+        if isinstance(self.shader, SoftSilhouetteShader):
+            if K <= 1:
+                raise ValueError("SoftSilhouetteShader needs a rasterizer with faces_per_pixel > 1")
+            a = ops.render_k_alpha(ndc, faces, H, W, K, blur, bp.sigma, cull_backfaces=rs.cull_backfaces)[None]
+            rgb = torch.ones(a.shape + (3,), device=a.device, dtype=a.dtype)
+            return torch.cat([rgb, a[..., None]], dim=-1)
+        faces_normals = meshes.verts_normals_packed()[meshes.faces_packed()]
+        return ops.render_k(ndc, faces, H, W, K, blur, faces_normals, bp.sigma, bp.gamma, cameras.znear, cameras.zfar, bp.background_color,
+                            cull_backfaces=rs.cull_backfaces, unit_bary=True)[None]
+
     def __call__(self, meshes_world, **kwargs):
+        if self.fused_render:
+            return self._render_fused(meshes_world, **kwargs)
         bp = kwargs.get("blend_params", getattr(self.shader, "blend_params", None))
         if bp is not None and "sigma" not in kwargs:
             kwargs = dict(kwargs, sigma=bp.sigma)

@@ -81,17 +81,23 @@ def raster_sil_bwd(verts_ndc, faces, sil_prod, grad_prod, blur_radius, sigma):
 
 
 # ------------------------------------------------------------------------------------------------ K-fragment rasteriser
-def _raster_k_args(verts_ndc, faces, H, W, K):
-    """Argument checks of raster_k_fwd / raster_k_bwd, before any device work."""
+def _raster_k_shapes(verts_ndc, faces, H, W, K, who="raster_k"):
+    """The shape, dtype and range checks of the K-fragment operators (no device is asked for)."""
     K, H, W = int(K), int(H), int(W)
     if K < 1 or K > L.RASTK_MAX_K:
-        raise ValueError(f"raster_k: K = {K} outside 1 .. {L.RASTK_MAX_K} (not clamped)")
+        raise ValueError(f"{who}: K = {K} outside 1 .. {L.RASTK_MAX_K} (not clamped)")
     if H < 1 or W < 1 or H > 8192 or W > 8192 or H * W > (1 << 25):
-        raise ValueError(f"raster_k: frame {H} x {W} out of range")
+        raise ValueError(f"{who}: frame {H} x {W} out of range")
     if verts_ndc.dim() != 2 or verts_ndc.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3 or not len(verts_ndc) or not len(faces):
-        raise ValueError("raster_k: expected (V,3) vertices and (F,3) faces")
+        raise ValueError(f"{who}: expected (V,3) vertices and (F,3) faces")
     if faces.dtype not in (torch.int32, torch.int64) or not faces.is_contiguous():
-        raise ValueError("raster_k: faces must be a contiguous int32 or int64 tensor")
+        raise ValueError(f"{who}: faces must be a contiguous int32 or int64 tensor")
+    return K, H, W
+
+
+def _raster_k_args(verts_ndc, faces, H, W, K):
+    """Argument checks of raster_k_fwd / raster_k_bwd, before any device work."""
+    K, H, W = _raster_k_shapes(verts_ndc, faces, H, W, K)
     _need_cuda(verts_ndc, faces)
     return K, H, W
 
@@ -178,6 +184,26 @@ def raster_k(verts_ndc, faces, H, W, K, blur_radius, cull_backfaces=False):
 
 
 # ------------------------------------------------------------------------------------------------ shading + blend of K-fragment planes
+def _blend_k_scalars(face_attr, sigma, gamma, znear, zfar, background, alpha_only, who="blend_k"):
+    """The checks of the blend's scalars, attributes and background (no device is asked for).  Returns (D, F, background array)."""
+    if not float(sigma) > 0.0:
+        raise ValueError(f"{who}: sigma must be positive")
+    D, F, bg = 1, 1, None
+    if not alpha_only:
+        if face_attr is None or face_attr.dim() != 3 or face_attr.shape[1] != 3 or face_attr.dtype != torch.float32 or not len(face_attr):
+            raise ValueError(f"{who}: face_attr must be a float32 tensor of shape (F,3,D)")
+        F, _, D = face_attr.shape
+        if D < 1 or D > L.RASTK_BLEND_MAX_D:
+            raise ValueError(f"{who}: D = {D} outside 1 .. {L.RASTK_BLEND_MAX_D}")
+        if not float(gamma) > 0.0 or not float(zfar) > float(znear):
+            raise ValueError(f"{who}: gamma must be positive and zfar above znear")
+        bg = [float(x) for x in (background.tolist() if torch.is_tensor(background) else background)]
+        if len(bg) != D:
+            raise ValueError(f"{who}: background has {len(bg)} entries, the face attributes {D} channels")
+        bg = (ctypes.c_float * D)(*bg)
+    return D, F, bg
+
+
 def _blend_k_args(pix_to_face, zbuf, bary, dists, face_attr, sigma, gamma, znear, zfar, background, unit_bary, alpha_only, grad_out=None):
     """Argument checks of blend_k_fwd / blend_k_bwd, before any device work.  Returns (H, W, K, D, F, flags, background array)."""
     if pix_to_face.dim() != 3 or pix_to_face.dtype != torch.int64:
@@ -195,21 +221,7 @@ def _blend_k_args(pix_to_face, zbuf, bary, dists, face_attr, sigma, gamma, znear
     for name, t, shape in planes:
         if t is None or tuple(t.shape) != shape or t.dtype != torch.float32:
             raise ValueError(f"blend_k: {name} must be a float32 tensor of shape {shape}")
-    if not float(sigma) > 0.0:
-        raise ValueError("blend_k: sigma must be positive")
-    D, F, bg = 1, 1, None
-    if not alpha_only:
-        if face_attr is None or face_attr.dim() != 3 or face_attr.shape[1] != 3 or face_attr.dtype != torch.float32 or not len(face_attr):
-            raise ValueError("blend_k: face_attr must be a float32 tensor of shape (F,3,D)")
-        F, _, D = face_attr.shape
-        if D < 1 or D > L.RASTK_BLEND_MAX_D:
-            raise ValueError(f"blend_k: D = {D} outside 1 .. {L.RASTK_BLEND_MAX_D}")
-        if not float(gamma) > 0.0 or not float(zfar) > float(znear):
-            raise ValueError("blend_k: gamma must be positive and zfar above znear")
-        bg = [float(x) for x in (background.tolist() if torch.is_tensor(background) else background)]
-        if len(bg) != D:
-            raise ValueError(f"blend_k: background has {len(bg)} entries, the face attributes {D} channels")
-        bg = (ctypes.c_float * D)(*bg)
+    D, F, bg = _blend_k_scalars(face_attr, sigma, gamma, znear, zfar, background, alpha_only)
     if grad_out is not None and tuple(grad_out.shape) != ((H, W) if alpha_only else (H, W, D + 1)):
         raise ValueError(f"blend_k_bwd: grad_out of shape {tuple(grad_out.shape)}")
     _need_cuda(grad_out, pix_to_face, dists, None if alpha_only else zbuf, None if alpha_only or unit_bary else bary, None if alpha_only else face_attr)
@@ -289,6 +301,120 @@ def blend_k_alpha(pix_to_face, dists, sigma):
     differentiable w.r.t. dists.  Bitwise the last channel of blend_k."""
     cfg = (float(sigma), 1.0, 0.0, 1.0, None, False, True)
     return _BlendKFn.apply(pix_to_face, None, None, dists, None, cfg)
+
+
+# ------------------------------------------------------------------------------------------------ fused K-fragment render (no planes)
+def _render_k_head(verts_ndc, faces, H, W, K, blur_radius, face_attr, sigma, gamma, znear, zfar, background, cull_backfaces, unit_bary,
+                   alpha_only, grad_out=None):
+    """Argument checks of render_k_fwd / render_k_bwd, before any device work (ValueError for shapes, dtypes and ranges, then FohoError
+    for CPU tensors), and the checked arguments both entry points of the library share (its C order) with the tensors they point into."""
+    K, H, W = _raster_k_shapes(verts_ndc, faces, H, W, K, "render_k")
+    if not float(blur_radius) >= 0.0:
+        raise ValueError("render_k: negative blur radius")
+    D, Fa, bg = _blend_k_scalars(face_attr, sigma, gamma, znear, zfar, background, alpha_only, "render_k")
+    if not alpha_only and Fa != len(faces):
+        raise ValueError(f"render_k: face_attr holds {Fa} faces, the mesh {len(faces)}")
+    if grad_out is not None and (tuple(grad_out.shape) != ((H, W) if alpha_only else (H, W, D + 1))):
+        raise ValueError(f"render_k_bwd: grad_out of shape {tuple(grad_out.shape)}")
+    _need_cuda(verts_ndc, faces, None if alpha_only else face_attr, grad_out)
+    keep = [_f32(verts_ndc), faces.detach().to(torch.int32), None if alpha_only else face_attr.detach().contiguous()]
+    V, F = keep[0].shape[0], keep[1].shape[0]
+    rflags = L.RASTK_CULL_BACKFACES if cull_backfaces else 0
+    bflags = (L.RASTK_BLEND_UNIT_BARY if unit_bary else 0) | (L.RASTK_BLEND_ALPHA_ONLY if alpha_only else 0)
+    head = [L._p(keep[0]), L._p(keep[1]), V, F, H, W, K, float(blur_radius), rflags, L._p(keep[2]), D, float(sigma), float(gamma),
+            float(znear), float(zfar), bg, bflags]
+    return (V, F, H, W, K, D), head, keep
+
+
+def render_k_fwd(verts_ndc, faces, H, W, K, blur_radius, face_attr, sigma, gamma, znear, zfar, background, cull_backfaces=False,
+                 unit_bary=False, alpha_only=False, list_cap=None):
+    """raster_k_fwd and blend_k_fwd in one (libfoho_rastk.so, foho_rastk_render_fwd): the K nearest fragments of every pixel are blended
+    where the rasteriser selects them, and the (H,W,K) planes never exist in memory.  Returns dict(out (H,W,D+1) [or (H,W) alpha with
+    alpha_only] -- bitwise blend_k_fwd on raster_k_fwd's planes --, counts (H,W) int32, workspace [the tile lists, which render_k_bwd
+    reads], list_cap, retried).  list_cap: as raster_k_fwd's -- one host read of the overflow word per call, and one repeat at the
+    exact size when the scene needs more."""
+    (V, F, H, W, K, D), head, keep = _render_k_head(verts_ndc, faces, H, W, K, blur_radius, face_attr, sigma, gamma, znear, zfar, background,
+                                                    cull_backfaces, unit_bary, alpha_only)
+    lib = L.rastk()
+    dev = keep[0].device
+    cap = int(list_cap) if list_cap is not None else max(4 * F, 1024)
+    out = torch.empty((H, W) if alpha_only else (H, W, D + 1), device=dev)
+    cn = torch.empty(H, W, dtype=torch.int32, device=dev)
+    ov = torch.zeros(1, dtype=torch.int32, device=dev)
+    retried = False
+    while True:
+        nws = lib.foho_rastk_workspace_bytes(V, F, H, W, K, cap)
+        if nws == 0:
+            raise L.FohoError(f"render_k_fwd: no workspace size for V={V} F={F} H={H} W={W} K={K} list_cap={cap}")
+        ws = torch.empty(nws, dtype=torch.uint8, device=dev)
+        L.rastk_check(lib.foho_rastk_render_fwd(*head, P(out.data_ptr()), P(cn.data_ptr()), P(ov.data_ptr()), cap, P(ws.data_ptr()), nws,
+                                                _stream(out)), "foho_rastk_render_fwd")
+        if not (int(ov.item()) & L.RASTK_OVER_LIST):      # one host read per call: the list size is data dependent
+            break
+        if retried:
+            raise L.FohoError("render_k_fwd: the tile lists overflowed again at the size the first pass reported")
+        cap, retried = int(ws[:8].view(torch.int64).item()), True
+    return dict(out=out, counts=cn, workspace=ws, list_cap=cap, retried=retried)
+
+
+def render_k_bwd(verts_ndc, faces, H, W, K, blur_radius, face_attr, sigma, gamma, znear, zfar, background, grad_out, workspace, list_cap,
+                 cull_backfaces=False, unit_bary=False, alpha_only=False, need=(True, True)):
+    """Backward of render_k_fwd over the workspace it returned (with its list_cap): (grad_verts_ndc (V,3), grad_face_attr (F,3,D)), None
+    where `need` is False (the library is handed a null pointer and skips that work) and, with alpha_only, for the attributes."""
+    (V, F, H, W, K, D), head, keep = _render_k_head(verts_ndc, faces, H, W, K, blur_radius, face_attr, sigma, gamma, znear, zfar, background,
+                                                    cull_backfaces, unit_bary, alpha_only, grad_out)
+    lib = L.rastk()
+    if workspace.dtype != torch.uint8 or workspace.dim() != 1 or not workspace.is_contiguous():
+        raise ValueError("render_k_bwd: workspace must be the uint8 tensor render_k_fwd returned")
+    _need_cuda(workspace)
+    need_bytes = lib.foho_rastk_workspace_bytes(V, F, H, W, K, int(list_cap))
+    if need_bytes == 0 or workspace.numel() < need_bytes:
+        raise ValueError(f"render_k_bwd: workspace of {workspace.numel()} bytes, list_cap {int(list_cap)} needs {need_bytes}")
+    go = _f32(grad_out)
+    dev = go.device
+    gv = torch.zeros(V, 3, device=dev) if need[0] else None
+    ga = torch.zeros(F, 3, D, device=dev) if need[1] and not alpha_only else None
+    if gv is not None or ga is not None:
+        L.rastk_check(lib.foho_rastk_render_bwd(*head, P(go.data_ptr()), L._p(gv), L._p(ga), int(list_cap), P(workspace.data_ptr()),
+                                                workspace.numel(), _stream(go)), "foho_rastk_render_bwd")
+    return gv, ga
+
+
+class _RenderKFn(torch.autograd.Function):
+    """render_k_fwd / render_k_bwd as one differentiable operator (w.r.t. verts_ndc and face_attr); the workspace is kept for the backward."""
+
+    @staticmethod
+    def forward(ctx, verts_ndc, faces, face_attr, geom, cfg):
+        r = render_k_fwd(verts_ndc, faces, *geom, face_attr, *cfg)
+        ctx.geom, ctx.cfg, ctx.list_cap = geom, cfg, r["list_cap"]
+        ctx.save_for_backward(verts_ndc.detach(), faces, None if face_attr is None else face_attr.detach(), r["workspace"])
+        ctx.mark_non_differentiable(r["counts"])
+        return r["out"], r["counts"]
+
+    @staticmethod
+    def backward(ctx, g_out, _gc):
+        v, f, a, ws = ctx.saved_tensors
+        gv, ga = render_k_bwd(v, f, *ctx.geom, a, *ctx.cfg[:5], g_out, ws, ctx.list_cap, *ctx.cfg[5:],
+                              need=(ctx.needs_input_grad[0], ctx.needs_input_grad[2]))
+        return (None if gv is None else gv.to(v.dtype)), None, ga, None, None
+
+
+def render_k(verts_ndc, faces, H, W, K, blur_radius, face_attr, sigma, gamma, znear, zfar, background, cull_backfaces=False, unit_bary=False,
+             return_counts=False):
+    """render_k_fwd's image (H,W,D+1), differentiable w.r.t. verts_ndc and face_attr: raster_k -> blend_k as one operator whose memory does
+    not grow with K.  The backward computes only the gradients autograd asks for.  Like raster_k it reads one word back per call and so
+    cannot be captured in a graph.  return_counts: also the (H,W) int32 fragment counts before the cut."""
+    bg = tuple(float(x) for x in (background.tolist() if torch.is_tensor(background) else background))
+    cfg = (float(sigma), float(gamma), float(znear), float(zfar), bg, bool(cull_backfaces), bool(unit_bary), False)
+    out, counts = _RenderKFn.apply(verts_ndc, faces, face_attr, (int(H), int(W), int(K), float(blur_radius)), cfg)
+    return (out, counts) if return_counts else out
+
+
+def render_k_alpha(verts_ndc, faces, H, W, K, blur_radius, sigma, cull_backfaces=False):
+    """(H,W) alpha = 1 - prod_k(1 - sigmoid(-dists_k / sigma)) over the K nearest fragments, mesh to silhouette in one operator,
+    differentiable w.r.t. verts_ndc.  Bitwise blend_k_alpha on raster_k's planes."""
+    cfg = (float(sigma), 1.0, 0.0, 1.0, None, bool(cull_backfaces), False, True)
+    return _RenderKFn.apply(verts_ndc, faces, None, (int(H), int(W), int(K), float(blur_radius)), cfg)[0]
 
 
 # ------------------------------------------------------------------------------------------------ knn / sdf
