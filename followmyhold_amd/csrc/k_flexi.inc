@@ -353,11 +353,12 @@ __global__ __launch_bounds__(256) void k_flexi_bwd(const float* x, const float* 
             const float D = sc[b] - sc[a];
             float dot = 0.f;
             for (int q = 0; q < 3; q++) dot += g[q] * (xc[3 * a + q] - xc[3 * b + q]);
-            const float inv2 = 1.0f / (D * D);
-            atomicAdd(&gs[ga], dot * sc[b] * inv2);
-            atomicAdd(&gs[gb], -dot * sc[a] * inv2);
+            // 1 / D^2 as two divisions: D * D underflows for |D| < 1e-19 while |s / D| <= 1 on a crossing edge, so (s / D) / D
+            // overflows only where the gradient itself does
+            const float wa = sc[b] / D, wb = -sc[a] / D;
+            atomicAdd(&gs[ga], dot * (wa / D));
+            atomicAdd(&gs[gb], dot * (wb / D));
             if (gx) {
-                const float wa = sc[b] / D, wb = -sc[a] / D;
                 for (int q = 0; q < 3; q++) {
                     atomicAdd(&gx[3 * ga + q], g[q] * wa);
                     atomicAdd(&gx[3 * gb + q], g[q] * wb);

@@ -21,7 +21,8 @@ def _grid(res, half=1.1):
 def _sdfs(x):
     r = x.norm(dim=1)
     torus = torch.stack([torch.sqrt(x[:, 0] ** 2 + x[:, 1] ** 2) - 0.6, x[:, 2]], 1).norm(dim=1) - 0.25
-    two = torch.minimum((x - 0.3).norm(dim=1) - 0.42, (x + 0.3).norm(dim=1) - 0.42)   # touching diagonally: ambiguous cubes
+    two = torch.minimum((x - 0.3).norm(dim=1) - 0.42, (x + 0.3).norm(dim=1) - 0.42)   # two components 0.2 apart on the diagonal;
+    # no cube of these four fields has more than one dual vertex: the multi-patch cases are test_flexi_grad.py's and the fuzz fields'
     noisy = r - 0.7 + 0.08 * torch.sin(9 * x[:, 0]) * torch.cos(7 * x[:, 1]) * torch.sin(5 * x[:, 2])
     return {"sphere": (r - 0.8, 2), "torus": (torus, 0), "two_spheres": (two, None), "bumpy": (noisy, 2)}
 
