@@ -5,11 +5,14 @@
  * The mesh foho_flexi_fwd (include/foho_hip.h) builds from a dense (res+1)^3 x 3 array of grid positions, built from three per-axis
  * coordinate tables instead, with work and memory outside the field proportional to the number of surface cubes (cubes whose 8
  * corners differ in sign under `s < 0`): the same vertices bit for bit, the same faces and l_dev, in the same order (vertices by
- * (cube, patch), faces by (axis, i, j, k) of their grid edge).  Forward only.
+ * (cube, patch), faces by (axis, i, j, k) of their grid edge).  foho_sflexi_mark and foho_sflexi_extract are the forward;
+ * foho_sflexi_bwd is the gradient of the vertices to the field, from what the forward left in the mark buffer and the cube workspace.
  *
  *   foho_sflexi_mark      the bit mask of the surface cubes, its prefix sums per 256 cubes, and the number of surface cubes
  *   foho_sflexi_extract   the mesh, from the mark buffer: ascending list of the surface cubes, case code and the three owned
  *                         grid edges per cube, one scan for the vertex and quad offsets, vertices and quads
+ *   foho_sflexi_bwd       dL/ds from dL/dvertices by gather: one thread per corner of a surface cube, the owner of a grid point sums
+ *                         its at most 24 terms in a fixed order and stores once
  *
  * The caller reads *n_cubes back between the two calls and sizes cube_cap, the cube workspace and the outputs from it (a surface
  * cube has at most 4 dual vertices and owns at most 3 quads = 6 triangles).
@@ -61,6 +64,18 @@ FOHO_SFLEXI_API int foho_sflexi_mark(const float* s, int32_t res, void* marks, s
 FOHO_SFLEXI_API int foho_sflexi_extract(const float* axes, const float* s, int32_t res, const void* marks, size_t marks_bytes,
                                         int32_t cube_cap, float* verts, int32_t verts_cap, int64_t* faces, int32_t faces_cap,
                                         float* l_dev, int32_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+
+/* dL/ds of the vertices foho_sflexi_extract wrote.  axes, s, res, marks, cube_cap and workspace: those of that call, the workspace as
+ * it left it.  grad_verts: n_verts x 3, dL/dvertices.  grad_s: (res+1)^3, ZEROED BY THE CALLER: every grid point that ends a sign-
+ * changing grid edge is written exactly once, with a plain store, and nothing else is touched.  Per cube, patch (dual vertex v, cnt
+ * crossing edges) and crossing edge (a, b) of the patch, with D = s_b - s_a and g = grad_verts[v] / cnt:
+ *   grad_s[a] += g . (x_a - x_b) (s_b / D) / D        grad_s[b] += g . (x_a - x_b) (-s_a / D) / D
+ * (foho_flexi_bwd's terms; x from the axis tables, so only the edge's own axis is left of the dot product).  No float atomics: a
+ * grid point's terms are summed in a fixed order, so grad_s is bitwise repeatable.  One launch, no host read: it can be captured in
+ * a graph.  cube_cap == 0 or n_verts == 0: success, nothing launched.  There is no gradient to the axis tables. */
+FOHO_SFLEXI_API int foho_sflexi_bwd(const float* axes, const float* s, int32_t res, const void* marks, size_t marks_bytes,
+                                    int32_t cube_cap, const float* grad_verts, int32_t n_verts, float* grad_s, const void* workspace,
+                                    size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

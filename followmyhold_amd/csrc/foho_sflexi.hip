@@ -16,6 +16,8 @@
 //                   (cube, patch), quad offsets by (axis, i, j, k): the dense orders.  off[n] is the vertex total
 //   k_sf_emit       vertices per surface cube (positions from the tables), quads per (axis, surface cube), the four ring cubes
 //                   through rank()
+//   k_sf_bwd        dL/ds from dL/dvertices (foho_sflexi_bwd), on what the kernels above left: 8 threads per surface cube, the owner
+//                   of a grid point gathers its at most 24 terms in a fixed order and stores once -- no float atomics
 // Compiled with foho_step.hip's flags (-ffp-contract=off, correctly rounded division and sqrt): the sign code, the dual vertex and
 // l_dev, the ring table and the quad's orientation and split are flexi_core.h's functions, the ones k_flexi.inc calls, which is what
 // makes the vertices, faces and l_dev bitwise the dense ones.  What is written here is what differs: corner positions from the axis
@@ -304,6 +306,74 @@ __global__ __launch_bounds__(TPB) void k_sf_emit(const float* __restrict__ axes,
         sf_faces_role((int64_t)(blockIdx.x - nvb) * TPB + threadIdx.x, n, res, mask, bpre, cid, cse, efl, off, faces, faces_cap, counts);
 }
 
+// dL/ds by gather: 8 threads per surface cube, one per corner.  Every grid point P that ends a crossing edge is a corner of a surface
+// cube; the thread whose cube has the lowest id among the marked cubes incident to P owns it.  The owner walks P's six grid edges
+// (axis 0 towards -, +, then axis 1, axis 2) and, on a crossing one, the in-grid cubes of the edge's ring in c_flexi_ring order: one
+// term of k_flexi_bwd per (edge, cube), at most 24, summed in that order into a register and stored once.  Positions come from the
+// axis tables, so of g . (x_a - x_b) only the edge's own axis is left.
+__global__ __launch_bounds__(TPB) void k_sf_bwd(const float* __restrict__ axes, const float* __restrict__ s, int res,
+                                                const uint64_t* __restrict__ mask, const int32_t* __restrict__ bpre,
+                                                const int32_t* __restrict__ total, int cube_cap, const int32_t* __restrict__ cid,
+                                                const uint8_t* __restrict__ cse, const int32_t* __restrict__ off,
+                                                const float* __restrict__ gverts, int n_verts, float* __restrict__ gs) {
+    const int n = *total;
+    if (n <= 0 || n > cube_cap) return;
+    const int64_t t = gid();
+    if (t >= 8 * (int64_t)n) return;
+    const int q = (int)(t & 7);
+    const int64_t cube = cid[t >> 3], C = (int64_t)res * res * res;
+    if (cube < 0 || cube >= C) return;
+    const int G = res + 1;
+    // the grid point
+    const int pt[3] = {(int)(cube / ((int64_t)res * res)) + (q & 1), (int)((cube / res) % res) + ((q >> 1) & 1), (int)(cube % res) + (q >> 2)};
+    // owner: no marked cube of a lower id among the in-grid cubes incident to P
+#pragma unroll
+    for (int o = 0; o < 8; o++) {
+        const int ci = pt[0] - (o & 1), cj = pt[1] - ((o >> 1) & 1), ck = pt[2] - (o >> 2);
+        if (ci < 0 || cj < 0 || ck < 0 || ci >= res || cj >= res || ck >= res) continue;
+        const int64_t other = ((int64_t)ci * res + cj) * res + ck;
+        if (other < cube && ((mask[other >> 6] >> (other & 63)) & 1ull)) return;
+    }
+    const float sp = s[((size_t)pt[0] * G + pt[1]) * G + pt[2]];
+    float acc = 0.f;
+    bool any = false;
+#pragma unroll
+    for (int axis = 0; axis < 3; axis++) {
+#pragma unroll
+        for (int side = 0; side < 2; side++) {
+            // the edge from M (its lower end, corner a) along +axis; P is a when side == 1
+            const int m = pt[axis] - 1 + side;
+            if (m < 0 || m >= res) continue;
+            const int mi = axis == 0 ? m : pt[0], mj = axis == 1 ? m : pt[1], mk = axis == 2 ? m : pt[2];
+            const int oi = mi + (axis == 0), oj = mj + (axis == 1), ok = mk + (axis == 2);
+            const float so = side ? s[((size_t)oi * G + oj) * G + ok] : s[((size_t)mi * G + mj) * G + mk];
+            if ((sp < 0.0f) == (so < 0.0f)) continue;
+            any = true;
+            const float sa = side ? sp : so, sb = side ? so : sp;
+            const float D = sb - sa;
+            // (s / D) / D as k_flexi_bwd: |s / D| <= 1 on a crossing edge
+            const float w = (side ? sb / D : -sa / D) / D;
+            const float dx = axes[axis * G + m] - axes[axis * G + m + 1];
+            for (int r = 0; r < 4; r++) {
+                const int ci = mi + c_flexi_ring[axis][r][0], cj = mj + c_flexi_ring[axis][r][1], ck = mk + c_flexi_ring[axis][r][2];
+                if (ci < 0 || cj < 0 || ck < 0 || ci >= res || cj >= res || ck >= res) continue;  // boundary edge: fewer than four cubes
+                const int rk = rank_of(mask, bpre, ((int64_t)ci * res + cj) * res + ck);
+                if ((unsigned)rk >= (unsigned)n) continue;  // (a mark buffer of another field)
+                const unsigned code = cse[rk];
+                const int p = c_flexi_edge_patch[code][c_flexi_ring[axis][r][3]];
+                if (p < 0) continue;  // (a workspace of another field)
+                const int v = off[rk] + p;
+                if ((unsigned)v >= (unsigned)n_verts) continue;
+                float cnt = 0.f;
+#pragma unroll
+                for (int e = 0; e < 12; e++) cnt += (c_flexi_edge_patch[code][e] == p) ? 1.0f : 0.0f;
+                acc += (gverts[3 * (size_t)v + axis] / cnt) * dx * w;
+            }
+        }
+    }
+    if (any) gs[((size_t)pt[0] * G + pt[1]) * G + pt[2]] = acc;
+}
+
 bool res_ok(int32_t r) { return r >= 1 && r <= FOHO_SFLEXI_MAX_RES; }
 bool cap_ok(int32_t c) { return c >= 0 && c <= FOHO_SFLEXI_MAX_CUBES; }
 
@@ -361,6 +431,23 @@ FOHO_SFLEXI_API int foho_sflexi_extract(const float* axes, const float* s, int32
     hipLaunchKernelGGL(k_sf_emit, dim3(nvb + blocks_for(3 * n, TPB)), dim3(TPB), 0, st, axes, s, res, m.mask, m.bpre, m.total, cube_cap, w.cid,
                        w.cse, w.efl, w.off, w.gtot, verts, l_dev, verts_cap, faces, faces_cap, counts, nvb);
     return launched("foho_sflexi_extract");
+}
+
+FOHO_SFLEXI_API int foho_sflexi_bwd(const float* axes, const float* s, int32_t res, const void* marks, size_t marks_bytes,
+                                    int32_t cube_cap, const float* grad_verts, int32_t n_verts, float* grad_s, const void* workspace,
+                                    size_t workspace_bytes, void* stream) {
+    if (!axes || !s || !marks || !grad_verts || !grad_s || !workspace) return fail(-1, "foho_sflexi_bwd: null argument");
+    if (!res_ok(res)) return fail(-1, "foho_sflexi_bwd: resolution outside 1 .. 1024");
+    if (!cap_ok(cube_cap)) return fail(-1, "foho_sflexi_bwd: bad capacity");
+    if (n_verts < 0) return fail(-1, "foho_sflexi_bwd: negative vertex count");
+    const MarkWs m = carve_mark(marks, res);
+    if (marks_bytes < m.bytes) return fail(-3, "foho_sflexi_bwd: mark buffer too small (query foho_sflexi_mark_bytes)");
+    const CubeWs w = carve_cube(const_cast<void*>(workspace), cube_cap);
+    if (workspace_bytes < w.bytes) return fail(-3, "foho_sflexi_bwd: workspace too small (query foho_sflexi_cube_bytes)");
+    if (cube_cap == 0 || n_verts == 0) return 0;
+    hipLaunchKernelGGL(k_sf_bwd, dim3(blocks_for(8 * (size_t)cube_cap, TPB)), dim3(TPB), 0, (hipStream_t)stream, axes, s, res, m.mask, m.bpre,
+                       m.total, cube_cap, w.cid, w.cse, w.off, grad_verts, n_verts, grad_s);
+    return launched("foho_sflexi_bwd");
 }
 
 }  // extern "C"

@@ -8,7 +8,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .sparse_flexi import flexicubes_sparse, grid_axes  # noqa: F401  (the forward-only extractor on axis tables: sparse_flexi.py)
+from .sparse_flexi import flexicubes_sparse, flexicubes_sparse_grad, grid_axes  # noqa: F401  (the extractors on axis tables: sparse_flexi.py)
 
 P = ctypes.c_void_p
 

@@ -124,6 +124,19 @@ def final_extract_mode(mode=None):
     return mode
 
 
+GUIDANCE_EXTRACTS = ("dense", "sparse")
+
+
+def guidance_extract_mode(mode=None):
+    """The extractor of the guidance loop's exact-size path: `mode`, else $FOHO_GUIDANCE_EXTRACT, else "dense" (ops.flexicubes on the
+    dense point grid).  "sparse" is sparse_flexi.flexicubes_sparse_grad on per-axis tables: the same mesh bit for bit, work and memory
+    proportional to the surface cubes, and a dL/dSDF that is bitwise repeatable.  Capacity mode (engine.SdfObjective) is untouched."""
+    mode = mode if mode is not None else (os.environ.get("FOHO_GUIDANCE_EXTRACT") or "dense")
+    if mode not in GUIDANCE_EXTRACTS:
+        raise E.L.FohoError(f"guidance_extract {mode!r}: one of {GUIDANCE_EXTRACTS}")
+    return mode
+
+
 def _require_hip_geo(vae):
     hip = getattr(vae, "hip_geo", None)
     if hip is None:
@@ -662,6 +675,8 @@ class GuidedShapePipeline:
             _require_hip_geo(self.vae)
         # "dense" (default) | "sparse": the final step's extractor (final_extract_mode); not in the signature either
         final_sparse = final_extract_mode(kwargs.pop("final_extract", None)) == "sparse"
+        # "dense" (default) | "sparse": the extractor of the guidance loop's exact-size path (guidance_extract_mode); not in the signature either
+        guid_sparse = guidance_extract_mode(kwargs.pop("guidance_extract", None)) == "sparse"
         # "dense" (default) | "hierarchical": how the guidance grid is decoded (latent2sdf_band), with guidance_decode_min_res; not in the
         # signature either
         guid_band = guidance_decode_mode(kwargs.pop("guidance_decode", None)) == "hierarchical"
@@ -674,6 +689,8 @@ class GuidedShapePipeline:
         self.stats = stats = {"inner_iterations": 0, "skipped_empty": 0}
         if guid_band:
             stats["guidance_decode"] = {}
+        if guid_sparse:
+            stats["guidance_extract"] = {"calls": 0, "cubes": 0, "vertices": 0, "faces": 0}
         self.loss_log = loss_log = []        # (phase, denoising step, iteration, loss terms) every 10th iteration, like the prints
         self.param_log = param_log = []      # (phase, denoising step, the 16 similarity parameters, noise prediction) at phase end
         device, dtype = self.device, self.dtype
@@ -819,7 +836,10 @@ class GuidedShapePipeline:
                     else:
                         cur = g2
                 if loss is None:
-                    verts, faces, _ = ops.flexicubes(xyz_samples, sdf, guid_res)
+                    if guid_sparse:      # the same mesh from axis tables; two host reads, so not for capacity mode's graph
+                        verts, faces, _, est = ops.flexicubes_sparse_grad(ops.grid_axes(bmin, bmax, guid_res), sdf, guid_res, return_stats=True)
+                    else:
+                        verts, faces, _ = ops.flexicubes(xyz_samples, sdf, guid_res)
                     if verts.shape[0] == 0:
                         print("Invalid mesh detected, aborting step!")
                         stats["skipped_empty"] += 1
@@ -827,6 +847,10 @@ class GuidedShapePipeline:
                     _bound_active_rows(self.vae, xyz_samples.shape[0])     # the exact-size path: no count known before the backward -- all rows
                     loss = gb.objective(verts, faces, cfg)
                     stats["exact_size_iterations"] = stats.get("exact_size_iterations", 0) + 1
+                    if guid_sparse:      # tallied with the iterations the extraction served
+                        stats["guidance_extract"]["calls"] += 1
+                        for key in ("cubes", "vertices", "faces"):
+                            stats["guidance_extract"][key] += est[key]
                 stats["inner_iterations"] += 1
                 if torch.isnan(loss):
                     print("Total loss is NaN")
