@@ -458,6 +458,10 @@ class LbsModel:
     """Device copy of a MANO-shaped model (synthetic.mano_like_model() or the real MANO arrays)."""
 
     def __init__(self, model, device="cuda"):
+        # k_lbs_joints walks the joints in index order and reads G[parents[i]]: a parent has to come before its child
+        parents = [int(p) for p in np.asarray(model["parents"]).reshape(-1)]
+        if len(parents) != 16 or parents[0] >= 0 or any(not 0 <= parents[i] < i for i in range(1, 16)):
+            raise L.FohoError(f"LbsModel: parents must be 16 entries with parents[0] < 0 and 0 <= parents[i] < i, got {parents}")
         t = lambda a, dt=torch.float32: torch.as_tensor(np.asarray(a)).to(dt).contiguous().to(device)
         self.v_template = t(model["v_template"])
         self.shapedirs = t(model["shapedirs"])

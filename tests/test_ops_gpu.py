@@ -60,7 +60,10 @@ def test_fused_intersection_count_equals_full_sdf_route():
 @gpu
 @pytest.mark.parametrize("B,use_mfma", [(3, 0), (3, 1), (32, -1)])
 def test_lbs_forward_and_backward(B, use_mfma):
-    """MANO-shaped LBS: forward vs the smplx restatement, backward vs torch autograd (VALU and matrix-core paths)."""
+    """MANO-shaped LBS on the dense synthetic model (no zero skinning weight: the wave skip of k_lbs_bwd_verts never fires here):
+    forward vs the float32 smplx restatement, backward vs its float32 torch autograd, each as ONE norm-relative error over the whole
+    tensor (VALU path, and the 16 x 16 matrix-core kernel at B = 3 and 32).  A coarse check: a fingertip joint's block of dL/drot
+    that is 0.5 % wrong passes it.  The per-block float64 comparison, sparse weights and the other tile paths are tests/test_lbs_grad.py."""
     from followmyhold_amd import ops
     m = synthetic.mano_like_model(1)
     mt = {k: torch.from_numpy(np.asarray(v)) for k, v in m.items()}
