@@ -71,6 +71,67 @@ N_KERNELS = 10
 ABI_VERSION = 105     # 105 = foho_vae_fwd / _bwd, foho_geo_weights.flags, foho_geo_gemm variant bits, FOHO_API visibility; 104 = foho_geo_weights.ln_{q,kv,2}_eps, foho_geo_decode_bwd_rows, foho_geo_prepare_queries / _decode_fwd_cached; include/foho_hip.h: 102 = foho_step_cfg.listed_cap, foho_step_desc.hand_order_valid, foho_abi_sizes; 103 = foho_geo_weights.q_norm / k_norm, foho_geo_abi_size
 
 
+# ------------------------------------------------------------------------------------------------ libfoho_hip.so
+# include/foho_hip.h, in its order: {function: (restype, argtypes)}.  int / int32_t -> c_i, int64_t -> c_l, size_t -> c_z,
+# float -> c_f, double -> c_d, every pointer or array -> vp (POINTER of the mirror for the step structs above; the mirrors of
+# geo_decode.py, sdpa.py and vae_transformer.py go in as ctypes.byref).  tests/test_cabi.py compares it with the header.
+c_l, c_z, c_d = ctypes.c_int64, ctypes.c_size_t, ctypes.c_double
+_DIMS, _DESC, _CFG = ctypes.POINTER(FohoDims), ctypes.POINTER(FohoStepDesc), ctypes.POINTER(FohoStepCfg)
+_WS = [vp, c_z, vp]                                                 # workspace, workspace_bytes, stream
+_ICP_TAIL = [c_i, c_i, c_i, c_d, c_d, vp, vp, vp] + _WS            # n_iter n_outliers fixed_scale, min_scale max_scale, T_out cost_out cost_history
+_LBS_MODEL = [vp, vp, vp, vp, vp, vp, c_i]                          # v_template shapedirs posedirs J_regressor lbs_weights parents, V
+_SIGNATURES = {
+    "foho_last_error": (ctypes.c_char_p, []), "foho_version": (c_i, []), "foho_abi_sizes": (c_i, [vp]),
+    "foho_step_workspace_bytes": (c_z, [_DIMS]), "foho_step_workspace_region": (c_l, [_DIMS, c_i, vp]),
+    "foho_step_run": (c_i, [_DESC, _CFG, c_i, vp]), "foho_step_finalize": (c_i, [_DESC, _CFG, vp]),
+    "foho_step_run_profiled": (c_i, [_DESC, _CFG, vp, vp]), "foho_kernel_name": (ctypes.c_char_p, [c_i]),
+    # verts_ndc faces, V F H W, blur_radius sigma, pix_to_face zbuf bary dists sil_prod overflow_flag
+    "foho_raster_fwd": (c_i, [vp, vp, c_i, c_i, c_i, c_i, c_f, c_f, vp, vp, vp, vp, vp, vp] + _WS),
+    "foho_raster_workspace_bytes": (c_z, [c_i, c_i, c_i, c_i]),
+    "foho_raster_bwd": (c_i, [vp, vp, c_i, c_i, c_i, c_i, vp, vp, vp, vp, vp, c_f, vp]),
+    "foho_raster_sil_bwd": (c_i, [vp, vp, c_i, c_i, c_i, c_i, vp, vp, vp, c_f, c_f, vp]),
+    "foho_knn1_fwd": (c_i, [vp, c_i, vp, c_i, vp, vp, vp]), "foho_point_mesh_dist": (c_i, [vp, vp, c_i, c_i, vp, c_i, vp, vp, vp]),
+    "foho_inside_points": (c_i, [vp, vp, c_i, c_i, vp, c_i, vp, vp]), "foho_lbs_workspace_bytes": (c_z, [c_i, c_i]),
+    "foho_lbs_fwd": (c_i, _LBS_MODEL + [vp, vp, c_i, c_i, vp, vp] + _WS),          # betas rot_mats, B use_mfma, verts joints
+    "foho_lbs_bwd": (c_i, _LBS_MODEL + [vp, c_i, vp, vp, vp, vp] + _WS),           # rot_mats, B, grad_verts grad_joints grad_betas grad_rot_mats
+    "foho_icp_workspace_bytes": (c_z, [c_i, c_i]), "foho_icp_run": (c_i, [vp, c_i, vp, c_i] + _ICP_TAIL),
+    "foho_icp_batch_workspace_bytes": (c_z, [c_i, c_i, c_i]), "foho_icp_run_batch": (c_i, [vp, c_i, c_i, vp, c_i] + _ICP_TAIL),
+    "foho_icp_surface_workspace_bytes": (c_z, [c_i, c_i, c_i]), "foho_icp_run_surface": (c_i, [vp, c_i, c_i, vp, c_i, vp, c_i] + _ICP_TAIL),
+    "foho_flexi_workspace_bytes": (c_z, [c_i]), "foho_topology_workspace_bytes": (c_z, [c_i]), "foho_object_workspace_bytes": (c_z, [c_i, c_i]),
+    "foho_flexi_fwd": (c_i, [vp, vp, c_i, vp, c_i, vp, c_i, vp, vp] + _WS),       # x s, res, verts verts_cap, faces faces_cap, l_dev counts
+    "foho_flexi_bwd": (c_i, [vp, vp, c_i, vp, c_i, vp, vp] + _WS),                 # x s, res, grad_verts n_verts, grad_s grad_x
+    "foho_topology_tables": (c_i, [vp, c_i, c_i, vp, vp, vp, vp, vp] + _WS),       # faces, V F, obj_flag inc_off inc_fc nbr_idx flag
+    "foho_object_update": (c_i, [_DESC, vp, vp, c_i, vp] + _WS),                   # desc, counts obj_faces, faces_cap, obj_flag
+    "foho_mesh_decimate": (c_i, [vp, c_i, vp, c_i, c_i, vp, vp, vp]),
+    # foho_geo_*: w first; chunk_rows is c_i, n_queries / row_cap are c_l, every *_bytes is c_z
+    "foho_geo_abi_size": (c_l, []), "foho_geo_workspace_bytes": (c_z, [vp, c_i]), "foho_geo_bwd_workspace_bytes": (c_z, [vp, c_i]),
+    "foho_geo_saved_bytes": (c_z, [vp, c_i, c_l]), "foho_geo_query_cache_bytes": (c_z, [vp, c_l]),
+    "foho_geo_rows_workspace_bytes": (c_z, [c_l, c_l, c_i]),
+    "foho_geo_prepare": (c_i, [vp, vp, c_i] + _WS), "foho_geo_set_kv": (c_i, [vp, vp, c_i] + _WS),
+    "foho_geo_decode_fwd": (c_i, [vp, vp, c_l, vp, c_i] + _WS),
+    "foho_geo_decode_fwd_keep": (c_i, [vp, vp, c_l, vp, c_i, vp, c_z, vp, c_z] + _WS),            # .. workspace, bwd_workspace, saved
+    "foho_geo_decode_bwd": (c_i, [vp, vp, c_l, vp, vp, c_i, vp, c_z, vp, c_z] + _WS),
+    "foho_geo_prepare_queries": (c_i, [vp, vp, c_l, c_i, vp, c_z] + _WS),                           # .. workspace, cache
+    "foho_geo_decode_fwd_cached": (c_i, [vp, vp, c_l, vp, c_z, vp, c_i] + _WS),
+    "foho_geo_decode_bwd_rows": (c_i, [vp, vp, c_l, vp, vp, c_l, c_i, vp, c_z, vp, c_z, vp, c_z, vp, vp]),   # .. rows_workspace, stats_out, stream
+    "foho_sdpa_workspace_bytes": (c_z, [c_i, c_i, c_i]),
+    "foho_sdpa_fwd": (c_i, [vp, vp, vp, vp, vp, vp, vp] + _WS),                    # d, q k v, out nlse lse_natural
+    "foho_sdpa_bwd": (c_i, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp] + _WS),        # d, q k v, out nlse, grad_out grad_q grad_k grad_v
+    "foho_vae_abi_size": (c_l, []), "foho_vae_workspace_bytes": (c_z, [vp]), "foho_vae_saved_bytes": (c_z, [vp]),
+    "foho_vae_fwd": (c_i, [vp, vp, vp, vp, c_z] + _WS), "foho_vae_bwd": (c_i, [vp, vp, vp, vp, c_z] + _WS),    # d, x0 out | grad_out grad_x0, workspace, saved
+    "foho_geo_gemm": (c_i, [vp, vp, vp, vp, vp, c_i, c_i, c_i, c_i, c_f, vp]),    # A Wt bias R C, M N K gelu, scale
+    "foho_geo_attention": (c_i, [vp, vp, vp, vp, c_i, c_i, c_i, vp]), "foho_geo_last_error": (ctypes.c_char_p, [])}
+
+
+def _declare(L, path, signatures):
+    for fn, (restype, argtypes) in signatures.items():
+        try:
+            f = getattr(L, fn)
+        except AttributeError:      # an older library of the same version number: additive entry points are recognised by their symbol
+            raise FohoError(f"{path} does not export {fn}: rebuild (make -C followmyhold_amd/csrc)") from None
+        f.restype, f.argtypes = restype, argtypes
+
+
 # the side libraries: libfoho_<name>.so exports foho_<name>_* (C ABI csrc/foho_<name>.h) and is of version FOHO_<NAME>_VERSION
 SIDE_VERSIONS = {"vol": 100, "sflexi": 100, "rastk": 101}      # rastk 101 = foho_rastk_blend_fwd / _bwd
 _sides = {}
@@ -97,22 +158,13 @@ def lib():
             raise FohoError(f"{SO_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                             "(there is no CPU fallback)")
         L = ctypes.CDLL(SO_PATH)
-        L.foho_last_error.restype = ctypes.c_char_p
-        L.foho_geo_last_error.restype = ctypes.c_char_p
-        L.foho_version.restype = ctypes.c_int
         sizes = (ctypes.c_int64 * 5)()
-        L.foho_abi_sizes.restype = ctypes.c_int
         ver = L.foho_abi_sizes(sizes)
         mine = [ctypes.sizeof(t) for t in (FohoImage, FohoDims, FohoRenderCfg, FohoStepCfg, FohoStepDesc)]
         if list(sizes) != mine or ver < ABI_VERSION:
             raise FohoError(f"{SO_PATH} is ABI version {ver} with struct sizes {list(sizes)}; this binding is version "
                             f"{ABI_VERSION} with {mine}: rebuild the library (python -c 'import __graft_entry__ as g; g.build()')")
-        L.foho_step_workspace_bytes.restype = ctypes.c_size_t
-        L.foho_step_workspace_bytes.argtypes = [ctypes.POINTER(FohoDims)]
-        L.foho_step_workspace_region.restype = ctypes.c_int64
-        L.foho_step_workspace_region.argtypes = [ctypes.POINTER(FohoDims), ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]
-        L.foho_step_run.restype = ctypes.c_int
-        L.foho_step_run.argtypes = [ctypes.POINTER(FohoStepDesc), ctypes.POINTER(FohoStepCfg), ctypes.c_int, vp]
+        _declare(L, SO_PATH, _SIGNATURES)
         _lib = L
     return _lib
 
@@ -146,12 +198,7 @@ def load_side(name, signatures):
         if ver() != version:
             raise FohoError(f"{path} is version {ver()}, this binding is {version}: rebuild (make -C followmyhold_amd/csrc)")
         getattr(L, f"foho_{name}_last_error").restype = ctypes.c_char_p
-        for fn, (restype, argtypes) in signatures.items():
-            try:
-                f = getattr(L, fn)
-            except AttributeError:      # an older library of the same version number: additive entry points are recognised by their symbol
-                raise FohoError(f"{path} does not export {fn}: rebuild (make -C followmyhold_amd/csrc)") from None
-            f.restype, f.argtypes = restype, argtypes
+        _declare(L, path, signatures)
         _sides[name] = L
     return L
 
@@ -161,13 +208,13 @@ def check_side(lib, prefix, status, what):
         raise FohoError(f"{what} failed ({status}): {getattr(lib, prefix + '_last_error')().decode()}")
 
 
-def _p(t):
-    return None if t is None else vp(t.data_ptr())
+def _p(t):      # a tensor's address, or None (NULL): the declared argtypes take the plain integer, no ctypes object per argument
+    return None if t is None else t.data_ptr()
 
 
 def _stream(device):
     import torch
-    return vp(torch.cuda.current_stream(device).cuda_stream)
+    return torch.cuda.current_stream(device).cuda_stream
 
 
 # ------------------------------------------------------------------------------------------------ libfoho_rastk.so

@@ -277,7 +277,6 @@ class GuidanceBatch:
             self.nbr_off, self.nbr_idx = self.inc_off, torch.zeros(3 * self.Ftot, dtype=torch.int32, device=dev)
             self.obj_counts = torch.zeros(B, 3, dtype=torch.int32, device=dev)           # actual (Vo, Fo, overflow bits)
             self.obj_faces64 = torch.zeros(B, self.obj_capacity[1], 3, dtype=torch.int64, device=dev)
-            self.lib.foho_object_workspace_bytes.restype = ctypes.c_size_t
             self.obj_ws = torch.zeros(self.lib.foho_object_workspace_bytes(self.Vtot, self.Ftot), dtype=torch.uint8, device=dev)
         elif topology == "deferred":    # the caller builds the incidence lists itself before the first step (TargetRenderer)
             ok = True
@@ -396,12 +395,9 @@ class GuidanceBatch:
         faces sit in obj_faces64 and whose counts sit in obj_counts (all on the device, as foho_flexi_fwd leaves them):
         image records, global face ids, topology tables, pair table, AABB.  Asynchronous, no host round trip."""
         if stream is None:
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-        P = ctypes.c_void_p
-        self.lib.foho_object_update.restype = ctypes.c_int
-        L.check(self.lib.foho_object_update(ctypes.byref(self.desc()), P(self.obj_counts.data_ptr()), P(self.obj_faces64.data_ptr()),
-                                            ctypes.c_int32(self.obj_capacity[1]), P(self.obj_flag.data_ptr()), P(self.obj_ws.data_ptr()),
-                                            ctypes.c_size_t(self.obj_ws.numel()), P(stream)), "foho_object_update")
+            stream = L._stream(self.device)
+        L.check(self.lib.foho_object_update(ctypes.byref(self.desc()), L._p(self.obj_counts), L._p(self.obj_faces64), self.obj_capacity[1],
+                                            L._p(self.obj_flag), L._p(self.obj_ws), self.obj_ws.numel(), stream), "foho_object_update")
 
     def obj_slot(self, b):
         """(first vertex slot, vertex capacity) of image b's object in verts_in / grad_verts_in."""
@@ -453,9 +449,9 @@ class GuidanceBatch:
             self._targets_dirty = False
         if stages:
             if stream is None:
-                stream = torch.cuda.current_stream(self.device).cuda_stream
+                stream = L._stream(self.device)
             cfg, _ = phase_cfg("C", do_update=False)
-            L.check(self.lib.foho_step_run(ctypes.byref(self.desc()), ctypes.byref(cfg), int(stages), ctypes.c_void_p(stream)),
+            L.check(self.lib.foho_step_run(ctypes.byref(self.desc()), ctypes.byref(cfg), int(stages), stream),
                     "foho_step_run(prepare)")
 
     def refresh_world(self, stream=None):
@@ -463,10 +459,10 @@ class GuidanceBatch:
         vertices first and updates the parameters last, so after a loop the region is one optimiser update behind; the
         reference builds its output meshes from the final parameters (PL:1614-1618, 1653-1657).  One vertex-stage call."""
         if stream is None:
-            stream = torch.cuda.current_stream(self.device).cuda_stream
+            stream = L._stream(self.device)
         self.prepare(stream)
         cfg, _ = phase_cfg("C", do_update=False)
-        L.check(self.lib.foho_step_run(ctypes.byref(self.desc()), ctypes.byref(cfg), int(L.STAGE_VERTEX), ctypes.c_void_p(stream)),
+        L.check(self.lib.foho_step_run(ctypes.byref(self.desc()), ctypes.byref(cfg), int(L.STAGE_VERTEX), stream),
                 "foho_step_run(VERTEX)")
 
     def fits(self, scenes):
@@ -607,9 +603,9 @@ class GuidanceBatch:
         """Recompute the AABB of the input meshes (centre of the similarity transform, PL:111).  Needed once and after
         every change of verts_in; the per-iteration step (STAGE_STEP) reuses it."""
         if stream is None:
-            stream = torch.cuda.current_stream(self.device).cuda_stream
+            stream = L._stream(self.device)
         cfg, _ = phase_cfg("C", do_update=False)
-        L.check(self.lib.foho_step_run(ctypes.byref(self.desc()), ctypes.byref(cfg), int(L.STAGE_BBOX), ctypes.c_void_p(stream)),
+        L.check(self.lib.foho_step_run(ctypes.byref(self.desc()), ctypes.byref(cfg), int(L.STAGE_BBOX), stream),
                 "foho_step_run(BBOX)")
         self._bbox_dirty = False
 
@@ -667,18 +663,14 @@ class GuidanceBatch:
         object vertices).  Returns False when the validity flag asks for the general path (one host read-back)."""
         lib, dev = self.lib, self.device
         Vtot, Ftot = int(self.Vtot), int(self.faces.shape[0])
-        lib.foho_topology_workspace_bytes.restype = ctypes.c_size_t
         nws = lib.foho_topology_workspace_bytes(Vtot)
         ws = torch.empty(nws, dtype=torch.uint8, device=dev)
         inc_off = torch.empty(Vtot + 1, dtype=torch.int32, device=dev)
         inc_fc = torch.empty(3 * Ftot, dtype=torch.int32, device=dev)
         nbr_idx = torch.empty(3 * Ftot if obj_flag is not None else 1, dtype=torch.int32, device=dev)
         flag = torch.zeros(1, dtype=torch.int32, device=dev)
-        P = ctypes.c_void_p
-        L.check(lib.foho_topology_tables(P(self.faces.data_ptr()), Vtot, Ftot, P(obj_flag.data_ptr()) if obj_flag is not None else None,
-                                         P(inc_off.data_ptr()), P(inc_fc.data_ptr()), P(nbr_idx.data_ptr()), P(flag.data_ptr()),
-                                         P(ws.data_ptr()), ctypes.c_size_t(nws),
-                                         P(torch.cuda.current_stream(dev).cuda_stream)), "foho_topology_tables")
+        L.check(lib.foho_topology_tables(L._p(self.faces), Vtot, Ftot, L._p(obj_flag), L._p(inc_off), L._p(inc_fc), L._p(nbr_idx), L._p(flag),
+                                         L._p(ws), nws, L._stream(dev)), "foho_topology_tables")
         if int(flag.item()) != 0:
             return False
         self.inc_off, self.inc_fc = inc_off, inc_fc
@@ -728,14 +720,14 @@ class GuidanceBatch:
     def step(self, cfg, stages=L.STAGE_STEP, stream=None):
         """One iteration for every image of the batch; asynchronous on the current stream."""
         if stream is None:
-            stream = torch.cuda.current_stream(self.device).cuda_stream
+            stream = L._stream(self.device)
         if self._bbox_dirty and (stages & L.STAGE_VERTEX):
             stages |= L.STAGE_BBOX
             self._bbox_dirty = False
         if self._targets_dirty and (stages & L.STAGE_LOSS):
             stages |= L.STAGE_TARGETS
             self._targets_dirty = False
-        L.check(self.lib.foho_step_run(ctypes.byref(self.desc()), ctypes.byref(cfg), int(stages), ctypes.c_void_p(stream)),
+        L.check(self.lib.foho_step_run(ctypes.byref(self.desc()), ctypes.byref(cfg), int(stages), stream),
                 "foho_step_run")
 
     def loss_dict(self, b=0):
@@ -817,8 +809,8 @@ class GuidanceBatch:
     def finalize(self, cfg, stream=None):
         """Apply the update a deferred_update step left pending (no-op when nothing is pending)."""
         if stream is None:
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-        L.check(self.lib.foho_step_finalize(ctypes.byref(self.desc()), ctypes.byref(cfg), ctypes.c_void_p(stream)),
+            stream = L._stream(self.device)
+        L.check(self.lib.foho_step_finalize(ctypes.byref(self.desc()), ctypes.byref(cfg), stream),
                 "foho_step_finalize")
 
     def step_profiled(self, cfg, deferred=False):
@@ -828,15 +820,13 @@ class GuidanceBatch:
         an iteration rides in the next k_xform); a finalize closes the pair."""
         lib = self.lib
         self.prepare()
-        lib.foho_step_run_profiled.restype = ctypes.c_int
-        lib.foho_kernel_name.restype = ctypes.c_char_p
         ms = (ctypes.c_float * L.N_KERNELS)()
-        stream = torch.cuda.current_stream(self.device).cuda_stream
+        stream = L._stream(self.device)
         c2 = cfg
         if deferred:
             c2 = L.FohoStepCfg.from_buffer_copy(bytes(cfg))
             c2.deferred_update = 2
-        L.check(lib.foho_step_run_profiled(ctypes.byref(self.desc()), ctypes.byref(c2), ctypes.c_void_p(stream), ms),
+        L.check(lib.foho_step_run_profiled(ctypes.byref(self.desc()), ctypes.byref(c2), stream, ms),
                 "foho_step_run_profiled")
         names = [lib.foho_kernel_name(i).decode() for i in range(L.N_KERNELS)]
         out = {n: float(ms[i]) for i, n in enumerate(names) if n}
@@ -883,7 +873,6 @@ class SdfObjective:
         self.sdf = torch.zeros(gb.B, G ** 3, device=dev)
         self.grad_sdf = torch.zeros(gb.B, G ** 3, device=dev)
         lib = gb.lib
-        lib.foho_flexi_workspace_bytes.restype = ctypes.c_size_t
         self.nws = int(lib.foho_flexi_workspace_bytes(self.res))
         self.flexi_ws = torch.zeros(gb.B, self.nws, dtype=torch.uint8, device=dev)
         self._graphs = {}
@@ -891,22 +880,20 @@ class SdfObjective:
 
     def enqueue(self, cfg):
         """The launch sequence of one iteration on the current stream (eager; the graph captures exactly this)."""
-        gb, lib, P = self.gb, self.gb.lib, ctypes.c_void_p
-        stream = P(torch.cuda.current_stream(gb.device).cuda_stream)
+        gb, lib, p = self.gb, self.gb.lib, L._p
+        stream = L._stream(gb.device)
         vcap, fcap = gb.obj_capacity
         for b in range(gb.B):
             lo, _ = gb.obj_slot(b)
-            L.check(lib.foho_flexi_fwd(P(self.xyz.data_ptr()), P(self.sdf[b].data_ptr()), self.res, P(gb.verts_in[lo:].data_ptr()), vcap,
-                                       P(gb.obj_faces64[b].data_ptr()), fcap, None, P(gb.obj_counts[b].data_ptr()),
-                                       P(self.flexi_ws[b].data_ptr()), ctypes.c_size_t(self.nws), stream), "foho_flexi_fwd")
+            L.check(lib.foho_flexi_fwd(p(self.xyz), p(self.sdf[b]), self.res, p(gb.verts_in[lo:]), vcap, p(gb.obj_faces64[b]), fcap, None,
+                                       p(gb.obj_counts[b]), p(self.flexi_ws[b]), self.nws, stream), "foho_flexi_fwd")
         gb.adopt_objects()
         gb.step(cfg)
         self.grad_sdf.fill_(0.0)        # a fill kernel (memset nodes inside a captured graph are not reliably ordered on this stack)
         for b in range(gb.B):
             lo, _ = gb.obj_slot(b)
-            L.check(lib.foho_flexi_bwd(P(self.xyz.data_ptr()), P(self.sdf[b].data_ptr()), self.res, P(gb.grad_verts_in[lo:].data_ptr()),
-                                       vcap, P(self.grad_sdf[b].data_ptr()), None, P(self.flexi_ws[b].data_ptr()),
-                                       ctypes.c_size_t(self.nws), stream), "foho_flexi_bwd")
+            L.check(lib.foho_flexi_bwd(p(self.xyz), p(self.sdf[b]), self.res, p(gb.grad_verts_in[lo:]), vcap, p(self.grad_sdf[b]), None,
+                                       p(self.flexi_ws[b]), self.nws, stream), "foho_flexi_bwd")
 
     def graph(self, cfg):
         key = (bytes(cfg), self.gb.workspace.data_ptr())     # a re-allocated workspace (set_n_renders) needs a new capture
@@ -1181,7 +1168,6 @@ class TargetRenderer:
                      hand_mask=np.zeros((H, W), bool), obj_mask=np.zeros((H, W), bool), fov=60.0, H=H, W=W)
         gb = self.gb = GuidanceBatch([dummy], device=device, n_renders=1, grid_res=2, topology="deferred")
         dev = gb.device
-        gb.lib.foho_topology_workspace_bytes.restype = ctypes.c_size_t
         self.topo_ws = torch.empty(gb.lib.foho_topology_workspace_bytes(self.vcap), dtype=torch.uint8, device=dev)
         self.flags = torch.zeros(2, dtype=torch.int32, device=dev)
         self.cfg, _ = phase_cfg("B", do_update=False)
@@ -1219,11 +1205,8 @@ class TargetRenderer:
         gb.verts_in[:v].copy_(pv[:v], non_blocking=True)
         gb.faces[:f].copy_(pf[:f], non_blocking=True)
         gb.images.copy_(pim, non_blocking=True)
-        P = ctypes.c_void_p
-        stream = torch.cuda.current_stream(gb.device).cuda_stream
-        L.check(gb.lib.foho_topology_tables(P(gb.faces.data_ptr()), v, f, None, P(gb.inc_off.data_ptr()), P(gb.inc_fc.data_ptr()),
-                                            P(gb.nbr_idx.data_ptr()), P(self.flags[1:].data_ptr()), P(self.topo_ws.data_ptr()),
-                                            ctypes.c_size_t(self.topo_ws.numel()), P(stream)), "foho_topology_tables")
+        L.check(gb.lib.foho_topology_tables(L._p(gb.faces), v, f, None, L._p(gb.inc_off), L._p(gb.inc_fc), L._p(gb.nbr_idx), L._p(self.flags[1:]),
+                                            L._p(self.topo_ws), self.topo_ws.numel(), L._stream(gb.device)), "foho_topology_tables")
         gb.flags.zero_()
         gb._bbox_dirty = True        # new vertices, and the scatter planes of THIS layout start clean
         gb.step(self.cfg, stages=L.STAGE_VERTEX | L.STAGE_RASTER)

@@ -78,7 +78,6 @@ class HipGeoDecoder:
 
     def __init__(self, parts, device="cuda", chunk_rows=None):
         self.lib = L.lib()
-        self.lib.foho_geo_abi_size.restype = ctypes.c_int64
         if int(self.lib.foho_geo_abi_size()) != ctypes.sizeof(FohoGeoWeights):
             raise L.FohoError(f"HipGeoDecoder: libfoho_hip.so was built with a foho_geo_weights of {int(self.lib.foho_geo_abi_size())} bytes, "
                               f"this binding's is {ctypes.sizeof(FohoGeoWeights)}: rebuild (make -C followmyhold_amd/csrc)")
@@ -148,9 +147,6 @@ class HipGeoDecoder:
         self._qcache = None               # (weakref to the query tensor, its version, shape, cache buffer)
         self._prepared = None
         self._ws_epoch = 0                # bumped by everything that rewrites the workspace's latent side (prepare, set_kv, a re-allocation)
-        for fn in (self.lib.foho_geo_workspace_bytes, self.lib.foho_geo_bwd_workspace_bytes):
-            fn.restype = ctypes.c_size_t
-            fn.argtypes = [ctypes.POINTER(FohoGeoWeights), ctypes.c_int32]
         if self.lib.foho_geo_workspace_bytes(ctypes.byref(w), self.chunk) == 0:
             raise L.FohoError(f"HipGeoDecoder: {L.geo_error()}")
 
@@ -164,9 +160,9 @@ class HipGeoDecoder:
         if lat.shape[1] != self.w.width:
             raise L.FohoError(f"HipGeoDecoder: latent tokens of width {lat.shape[1]}, decoder of width {self.w.width}")
         self._size_for(lat.shape[0])
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        L.geo_check(self.lib.foho_geo_prepare(ctypes.byref(self.w), L.vp(lat.data_ptr()), ctypes.c_int32(self.chunk), L.vp(self.workspace.data_ptr()),
-                                              ctypes.c_size_t(self.workspace.numel()), L.vp(stream)), "foho_geo_prepare")
+        stream = L._stream(self.device)
+        L.geo_check(self.lib.foho_geo_prepare(ctypes.byref(self.w), L._p(lat), self.chunk, L._p(self.workspace), self.workspace.numel(), stream),
+                    "foho_geo_prepare")
         self._lat = lat        # kept alive until the stream has consumed it
         self._ws_epoch += 1
 
@@ -199,9 +195,9 @@ class HipGeoDecoder:
         if kv.dim() != 2 or kv.shape[1] != 2 * self.w.width:
             raise L.FohoError(f"HipGeoDecoder: kv of shape {tuple(kv.shape)}, decoder of width {self.w.width}")
         self._size_for(kv.shape[0])
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        L.geo_check(self.lib.foho_geo_set_kv(ctypes.byref(self.w), L.vp(kv.data_ptr()), ctypes.c_int32(self.chunk), L.vp(self.workspace.data_ptr()),
-                                             ctypes.c_size_t(self.workspace.numel()), L.vp(stream)), "foho_geo_set_kv")
+        stream = L._stream(self.device)
+        L.geo_check(self.lib.foho_geo_set_kv(ctypes.byref(self.w), L._p(kv), self.chunk, L._p(self.workspace), self.workspace.numel(), stream),
+                    "foho_geo_set_kv")
         self._prepared = None
         self._ws_epoch += 1
 
@@ -233,16 +229,14 @@ class HipGeoDecoder:
         """decode() for a forward whose backward will follow: -> (logits (N,) float32, saved), `saved` = the activations
         decode_bwd needs (18 KB per query at width 1024: 5 GB for a 65^3 grid), so that it does not recompute them."""
         q = queries.reshape(-1, 3).to(self.device, torch.float32).contiguous()
-        self.lib.foho_geo_saved_bytes.restype = ctypes.c_size_t
-        n = int(self.lib.foho_geo_saved_bytes(ctypes.byref(self.w), ctypes.c_int32(self.chunk), ctypes.c_int64(q.shape[0])))
+        n = int(self.lib.foho_geo_saved_bytes(ctypes.byref(self.w), self.chunk, q.shape[0]))
         saved = torch.empty(n, dtype=torch.uint8, device=self.device)
         out = torch.empty(q.shape[0], dtype=torch.float32, device=self.device)
         bws = self._bwd_ws()
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        L.geo_check(self.lib.foho_geo_decode_fwd_keep(ctypes.byref(self.w), L.vp(q.data_ptr()), ctypes.c_int64(q.shape[0]), L.vp(out.data_ptr()),
-                                                      ctypes.c_int32(self.chunk), L.vp(self.workspace.data_ptr()), ctypes.c_size_t(self.workspace.numel()),
-                                                      L.vp(bws.data_ptr()), ctypes.c_size_t(bws.numel()), L.vp(saved.data_ptr()),
-                                                      ctypes.c_size_t(saved.numel()), L.vp(stream)), "foho_geo_decode_fwd_keep")
+        stream = L._stream(self.device)
+        L.geo_check(self.lib.foho_geo_decode_fwd_keep(ctypes.byref(self.w), L._p(q), q.shape[0], L._p(out), self.chunk, L._p(self.workspace),
+                                                      self.workspace.numel(), L._p(bws), bws.numel(), L._p(saved), saved.numel(), stream),
+                    "foho_geo_decode_fwd_keep")
         return out, saved
 
     def decode_bwd(self, queries, grad_logits, saved=None):
@@ -254,12 +248,10 @@ class HipGeoDecoder:
             raise L.FohoError(f"HipGeoDecoder: {q.shape[0]} queries, {g.shape[0]} logit gradients")
         bws = self._bwd_ws()
         out = torch.empty(self.w.n_latents, 2 * self.w.width, dtype=torch.float32, device=self.device)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        L.geo_check(self.lib.foho_geo_decode_bwd(ctypes.byref(self.w), L.vp(q.data_ptr()), ctypes.c_int64(q.shape[0]), L.vp(g.data_ptr()),
-                                                 L.vp(out.data_ptr()), ctypes.c_int32(self.chunk), L.vp(self.workspace.data_ptr()),
-                                                 ctypes.c_size_t(self.workspace.numel()), L.vp(bws.data_ptr()), ctypes.c_size_t(bws.numel()),
-                                                 L.vp(saved.data_ptr()) if saved is not None else None,
-                                                 ctypes.c_size_t(saved.numel() if saved is not None else 0), L.vp(stream)), "foho_geo_decode_bwd")
+        stream = L._stream(self.device)
+        L.geo_check(self.lib.foho_geo_decode_bwd(ctypes.byref(self.w), L._p(q), q.shape[0], L._p(g), L._p(out), self.chunk, L._p(self.workspace),
+                                                 self.workspace.numel(), L._p(bws), bws.numel(), L._p(saved),
+                                                 saved.numel() if saved is not None else 0, stream), "foho_geo_decode_bwd")
         return out
 
     def decode_bwd_rows(self, queries, grad_logits, row_cap=None):
@@ -273,19 +265,16 @@ class HipGeoDecoder:
         n = q.shape[0]
         cap = int(row_cap or self.row_cap or n)
         cap = n if cap <= 0 or cap > n else cap
-        self.lib.foho_geo_rows_workspace_bytes.restype = ctypes.c_size_t
-        need = int(self.lib.foho_geo_rows_workspace_bytes(ctypes.c_int64(n), ctypes.c_int64(cap), ctypes.c_int32(self.chunk)))
+        need = int(self.lib.foho_geo_rows_workspace_bytes(n, cap, self.chunk))
         if getattr(self, "_rows_ws", None) is None or self._rows_ws.numel() < need:
             self._rows_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         bws = self._bwd_ws()
         out = torch.empty(self.w.n_latents, 2 * self.w.width, dtype=torch.float32, device=self.device)
         stats = torch.zeros(2, dtype=torch.int32, device=self.device)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        L.geo_check(self.lib.foho_geo_decode_bwd_rows(ctypes.byref(self.w), L.vp(q.data_ptr()), ctypes.c_int64(n), L.vp(g.data_ptr()), L.vp(out.data_ptr()),
-                                                      ctypes.c_int64(cap), ctypes.c_int32(self.chunk), L.vp(self.workspace.data_ptr()),
-                                                      ctypes.c_size_t(self.workspace.numel()), L.vp(bws.data_ptr()), ctypes.c_size_t(bws.numel()),
-                                                      L.vp(self._rows_ws.data_ptr()), ctypes.c_size_t(self._rows_ws.numel()), L.vp(stats.data_ptr()),
-                                                      L.vp(stream)), "foho_geo_decode_bwd_rows")
+        stream = L._stream(self.device)
+        L.geo_check(self.lib.foho_geo_decode_bwd_rows(ctypes.byref(self.w), L._p(q), n, L._p(g), L._p(out), cap, self.chunk, L._p(self.workspace),
+                                                      self.workspace.numel(), L._p(bws), bws.numel(), L._p(self._rows_ws), self._rows_ws.numel(),
+                                                      L._p(stats), stream), "foho_geo_decode_bwd_rows")
         self.last_row_stats = stats
         if self.rows_dropped_total is None:
             self.rows_dropped_total = torch.zeros(1, dtype=torch.int32, device=self.device)
@@ -309,13 +298,11 @@ class HipGeoDecoder:
             raise L.FohoError("HipGeoDecoder.prepare_queries: a contiguous float32 tensor on the decoder's device (it is cached by identity)")
         if self.workspace is None:
             self._size_for(self.w.n_latents)
-        self.lib.foho_geo_query_cache_bytes.restype = ctypes.c_size_t
-        need = int(self.lib.foho_geo_query_cache_bytes(ctypes.byref(self.w), ctypes.c_int64(q.shape[0])))
+        need = int(self.lib.foho_geo_query_cache_bytes(ctypes.byref(self.w), q.shape[0]))
         buf = torch.empty(need, dtype=torch.uint8, device=self.device)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        L.geo_check(self.lib.foho_geo_prepare_queries(ctypes.byref(self.w), L.vp(q.data_ptr()), ctypes.c_int64(q.shape[0]), ctypes.c_int32(self.chunk),
-                                                      L.vp(self.workspace.data_ptr()), ctypes.c_size_t(self.workspace.numel()), L.vp(buf.data_ptr()),
-                                                      ctypes.c_size_t(need), L.vp(stream)), "foho_geo_prepare_queries")
+        stream = L._stream(self.device)
+        L.geo_check(self.lib.foho_geo_prepare_queries(ctypes.byref(self.w), L._p(q), q.shape[0], self.chunk, L._p(self.workspace),
+                                                      self.workspace.numel(), L._p(buf), need, stream), "foho_geo_prepare_queries")
         # keyed by storage address + version + size, with the tensor kept alive (so the address cannot be handed to another one)
         self._qcache = (queries, queries._version, buf)
         return buf
@@ -340,8 +327,7 @@ class HipGeoDecoder:
         if g is not None and g[0] is xyz and g[1] == xyz._version:
             return g[2]
         q = xyz.to(self.device).half().float().reshape(1, -1, 3).contiguous()
-        self.lib.foho_geo_query_cache_bytes.restype = ctypes.c_size_t
-        if int(self.lib.foho_geo_query_cache_bytes(ctypes.byref(self.w), ctypes.c_int64(q.shape[1]))) <= self.query_cache_limit:
+        if int(self.lib.foho_geo_query_cache_bytes(ctypes.byref(self.w), q.shape[1])) <= self.query_cache_limit:
             self.prepare_queries(q)
         else:
             self._qcache = None
@@ -353,16 +339,14 @@ class HipGeoDecoder:
         cache = self._cached_queries(queries)
         q = queries.reshape(-1, 3).to(self.device, torch.float32).contiguous()
         out = torch.empty(q.shape[0], dtype=torch.float32, device=self.device)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
+        stream = L._stream(self.device)
         if cache is not None:
-            L.geo_check(self.lib.foho_geo_decode_fwd_cached(ctypes.byref(self.w), L.vp(q.data_ptr()), ctypes.c_int64(q.shape[0]), L.vp(cache.data_ptr()),
-                                                            ctypes.c_size_t(cache.numel()), L.vp(out.data_ptr()), ctypes.c_int32(self.chunk),
-                                                            L.vp(self.workspace.data_ptr()), ctypes.c_size_t(self.workspace.numel()), L.vp(stream)),
+            L.geo_check(self.lib.foho_geo_decode_fwd_cached(ctypes.byref(self.w), L._p(q), q.shape[0], L._p(cache), cache.numel(), L._p(out),
+                                                            self.chunk, L._p(self.workspace), self.workspace.numel(), stream),
                         "foho_geo_decode_fwd_cached")
             return out
-        L.geo_check(self.lib.foho_geo_decode_fwd(ctypes.byref(self.w), L.vp(q.data_ptr()), ctypes.c_int64(q.shape[0]), L.vp(out.data_ptr()),
-                                                 ctypes.c_int32(self.chunk), L.vp(self.workspace.data_ptr()), ctypes.c_size_t(self.workspace.numel()),
-                                                 L.vp(stream)), "foho_geo_decode_fwd")
+        L.geo_check(self.lib.foho_geo_decode_fwd(ctypes.byref(self.w), L._p(q), q.shape[0], L._p(out), self.chunk, L._p(self.workspace),
+                                                 self.workspace.numel(), stream), "foho_geo_decode_fwd")
         return out
 
     def __call__(self, queries, latents):

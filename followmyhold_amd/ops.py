@@ -8,13 +8,8 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from ._lib import _p, _stream
 from .sparse_flexi import flexicubes_sparse, flexicubes_sparse_grad, grid_axes  # noqa: F401  (the extractors on axis tables: sparse_flexi.py)
-
-P = ctypes.c_void_p
-
-
-def _stream(t):
-    return P(torch.cuda.current_stream(t.device).cuda_stream)
 
 
 def _need_cuda(*ts):
@@ -36,7 +31,6 @@ def raster_fwd(verts_ndc, faces, H, W, blur_radius, sigma=1e-8, want_sil=True):
     v, f = _f32(verts_ndc), faces.detach().to(torch.int32).contiguous()
     V, F = v.shape[0], f.shape[0]
     dev = v.device
-    lib.foho_raster_workspace_bytes.restype = ctypes.c_size_t
     nws = lib.foho_raster_workspace_bytes(V, F, H, W)
     ws = torch.empty(nws, dtype=torch.uint8, device=dev)
     p2f = torch.empty(H, W, dtype=torch.int64, device=dev)
@@ -44,10 +38,8 @@ def raster_fwd(verts_ndc, faces, H, W, blur_radius, sigma=1e-8, want_sil=True):
     ba = torch.empty(H, W, 3, device=dev)
     pr = torch.empty(H, W, device=dev) if want_sil else None
     ov = torch.zeros(1, dtype=torch.int32, device=dev)
-    L.check(lib.foho_raster_fwd(P(v.data_ptr()), P(f.data_ptr()), V, F, H, W, ctypes.c_float(blur_radius),
-                                ctypes.c_float(sigma), P(p2f.data_ptr()), P(zb.data_ptr()), P(ba.data_ptr()),
-                                P(di.data_ptr()), P(pr.data_ptr()) if want_sil else None, P(ov.data_ptr()),
-                                P(ws.data_ptr()), ctypes.c_size_t(nws), _stream(v)), "foho_raster_fwd")
+    L.check(lib.foho_raster_fwd(_p(v), _p(f), V, F, H, W, blur_radius, sigma, _p(p2f), _p(zb), _p(ba), _p(di), _p(pr), _p(ov),
+                                _p(ws), nws, _stream(dev)), "foho_raster_fwd")
     return dict(pix_to_face=p2f, zbuf=zb, bary=ba, dists=di, sil_prod=pr, overflow=ov, _keep=(v, f, ws))
 
 
@@ -61,10 +53,8 @@ def raster_bwd(verts_ndc, faces, pix_to_face, grad_zbuf=None, grad_bary=None, gr
     gb = _f32(grad_bary) if grad_bary is not None else None
     gd = _f32(grad_dists) if grad_dists is not None else None
     p2f = pix_to_face.contiguous()
-    L.check(lib.foho_raster_bwd(P(v.data_ptr()), P(f.data_ptr()), v.shape[0], f.shape[0], H, W, P(p2f.data_ptr()),
-                                P(gz.data_ptr()) if gz is not None else None, P(gb.data_ptr()) if gb is not None else None,
-                                P(gd.data_ptr()) if gd is not None else None, P(g.data_ptr()), ctypes.c_float(blur_radius),
-                                _stream(v)), "foho_raster_bwd")
+    L.check(lib.foho_raster_bwd(_p(v), _p(f), v.shape[0], f.shape[0], H, W, _p(p2f), _p(gz), _p(gb), _p(gd), _p(g), blur_radius,
+                                _stream(v.device)), "foho_raster_bwd")
     return g
 
 
@@ -75,8 +65,8 @@ def raster_sil_bwd(verts_ndc, faces, sil_prod, grad_prod, blur_radius, sigma):
     H, W = sil_prod.shape[-2:]
     g = torch.zeros_like(v)
     pr, gp = _f32(sil_prod), _f32(grad_prod)
-    L.check(lib.foho_raster_sil_bwd(P(v.data_ptr()), P(f.data_ptr()), v.shape[0], f.shape[0], H, W, P(pr.data_ptr()), P(gp.data_ptr()),
-                                    P(g.data_ptr()), ctypes.c_float(blur_radius), ctypes.c_float(sigma), _stream(v)), "foho_raster_sil_bwd")
+    L.check(lib.foho_raster_sil_bwd(_p(v), _p(f), v.shape[0], f.shape[0], H, W, _p(pr), _p(gp), _p(g), blur_radius, sigma,
+                                    _stream(v.device)), "foho_raster_sil_bwd")
     return g
 
 
@@ -102,6 +92,25 @@ def _raster_k_args(verts_ndc, faces, H, W, K):
     return K, H, W
 
 
+def _with_tile_lists(who, shape, cap, ov, launch):
+    """launch(cap, workspace) of raster_k_fwd / render_k_fwd (`who`) with a workspace whose per-tile face lists hold `cap` entries, and,
+    when the overflow word `ov` says afterwards that they were too short, once more at the size the first pass left in the workspace.
+    Returns (workspace, cap, retried)."""
+    V, F, H, W, K = shape
+    retried = False
+    while True:
+        nws = L.rastk().foho_rastk_workspace_bytes(V, F, H, W, K, cap)
+        if nws == 0:
+            raise L.FohoError(f"{who}: no workspace size for V={V} F={F} H={H} W={W} K={K} list_cap={cap}")
+        ws = torch.empty(nws, dtype=torch.uint8, device=ov.device)
+        launch(cap, ws)
+        if not (int(ov.item()) & L.RASTK_OVER_LIST):      # one host read per call: the list size is data dependent
+            return ws, cap, retried
+        if retried:
+            raise L.FohoError(f"{who}: the tile lists overflowed again at the size the first pass reported")
+        cap, retried = int(ws[:8].view(torch.int64).item()), True
+
+
 def raster_k_fwd(verts_ndc, faces, H, W, K, blur_radius, cull_backfaces=False, list_cap=None):
     """pytorch3d rasterize_meshes(faces_per_pixel=K) for one mesh, materialised (libfoho_rastk.so; 1 <= K <= 128).
     Returns dict(pix_to_face (H,W,K) int64, zbuf (H,W,K), bary (H,W,K,3), dists (H,W,K), counts (H,W) int32 [fragments the pixel
@@ -119,21 +128,12 @@ def raster_k_fwd(verts_ndc, faces, H, W, K, blur_radius, cull_backfaces=False, l
     cn = torch.empty(H, W, dtype=torch.int32, device=dev)
     ov = torch.zeros(1, dtype=torch.int32, device=dev)
     flags = L.RASTK_CULL_BACKFACES if cull_backfaces else 0
-    retried = False
-    while True:
-        nws = lib.foho_rastk_workspace_bytes(V, F, H, W, K, cap)
-        if nws == 0:
-            raise L.FohoError(f"raster_k_fwd: no workspace size for V={V} F={F} H={H} W={W} K={K} list_cap={cap}")
-        ws = torch.empty(nws, dtype=torch.uint8, device=dev)
-        L.rastk_check(lib.foho_rastk_fwd(P(v.data_ptr()), P(f.data_ptr()), V, F, H, W, K, float(blur_radius), flags, P(p2f.data_ptr()),
-                                         P(zb.data_ptr()), P(ba.data_ptr()), P(di.data_ptr()), P(cn.data_ptr()), P(ov.data_ptr()), cap,
-                                         P(ws.data_ptr()), nws, _stream(v)), "foho_rastk_fwd")
-        if not (int(ov.item()) & L.RASTK_OVER_LIST):      # one host read per call: the list size is data dependent
-            break
-        if retried:
-            raise L.FohoError("raster_k_fwd: the tile lists overflowed again at the size the first pass reported")
-        cap, retried = int(ws[:8].view(torch.int64).item()), True
-    return dict(pix_to_face=p2f, zbuf=zb, bary=ba, dists=di, counts=cn, retried=retried, list_cap=cap, workspace_bytes=int(nws))
+
+    def launch(cap, ws):
+        L.rastk_check(lib.foho_rastk_fwd(_p(v), _p(f), V, F, H, W, K, float(blur_radius), flags, _p(p2f), _p(zb), _p(ba), _p(di), _p(cn),
+                                         _p(ov), cap, _p(ws), ws.numel(), _stream(dev)), "foho_rastk_fwd")
+    ws, cap, retried = _with_tile_lists("raster_k_fwd", (V, F, H, W, K), cap, ov, launch)
+    return dict(pix_to_face=p2f, zbuf=zb, bary=ba, dists=di, counts=cn, retried=retried, list_cap=cap, workspace_bytes=ws.numel())
 
 
 def raster_k_bwd(verts_ndc, faces, pix_to_face, grad_zbuf=None, grad_bary=None, grad_dists=None, blur_radius=0.0):
@@ -153,10 +153,8 @@ def raster_k_bwd(verts_ndc, faces, pix_to_face, grad_zbuf=None, grad_bary=None, 
         if t is not None and tuple(t.shape) != shape:
             raise ValueError(f"raster_k_bwd: gradient of shape {tuple(t.shape)}, expected {shape}")
     p2f = pix_to_face.contiguous()
-    L.rastk_check(lib.foho_rastk_bwd(P(v.data_ptr()), P(f.data_ptr()), v.shape[0], f.shape[0], H, W, K, P(p2f.data_ptr()),
-                                     P(gz.data_ptr()) if gz is not None else None, P(gb.data_ptr()) if gb is not None else None,
-                                     P(gd.data_ptr()) if gd is not None else None, P(g.data_ptr()), float(blur_radius), _stream(v)),
-                  "foho_rastk_bwd")
+    L.rastk_check(lib.foho_rastk_bwd(_p(v), _p(f), v.shape[0], f.shape[0], H, W, K, _p(p2f), _p(gz), _p(gb), _p(gd), _p(g), float(blur_radius),
+                                     _stream(v.device)), "foho_rastk_bwd")
     return g
 
 
@@ -236,7 +234,7 @@ def _blend_k_head(pix_to_face, zbuf, bary, dists, face_attr, sigma, gamma, znear
     keep = [pix_to_face.contiguous(), None if alpha_only else zbuf.detach().contiguous(),
             None if alpha_only or unit_bary else bary.detach().contiguous(), dists.detach().contiguous(),
             None if alpha_only else face_attr.detach().contiguous()]
-    head = [L._p(t) for t in keep] + [F, H, W, K, D, float(sigma), float(gamma), float(znear), float(zfar), bg, flags]
+    head = [_p(t) for t in keep] + [F, H, W, K, D, float(sigma), float(gamma), float(znear), float(zfar), bg, flags]
     return (H, W, K, D, F), head, keep
 
 
@@ -249,7 +247,7 @@ def blend_k_fwd(pix_to_face, zbuf, bary, dists, face_attr, sigma, gamma, znear, 
     (H, W, K, D, F), head, keep = _blend_k_head(pix_to_face, zbuf, bary, dists, face_attr, sigma, gamma, znear, zfar, background, unit_bary,
                                                 alpha_only)
     out = torch.empty((H, W) if alpha_only else (H, W, D + 1), device=dists.device)
-    L.rastk_check(L.rastk().foho_rastk_blend_fwd(*head, P(out.data_ptr()), _stream(dists)), "foho_rastk_blend_fwd")
+    L.rastk_check(L.rastk().foho_rastk_blend_fwd(*head, _p(out), _stream(dists.device)), "foho_rastk_blend_fwd")
     return out
 
 
@@ -269,7 +267,7 @@ def blend_k_bwd(pix_to_face, zbuf, bary, dists, face_attr, sigma, gamma, znear, 
     # the plane gradients are written at the pixels' fragments only: zeroed buffers
     shapes = ((H, W, K), (H, W, K, 3), (H, W, K), (F, 3, D))
     grads = [torch.zeros(s, device=dev) if n else None for s, n in zip(shapes, need)]
-    L.rastk_check(L.rastk().foho_rastk_blend_bwd(*head, P(go.data_ptr()), *[L._p(g) for g in grads], _stream(dists)), "foho_rastk_blend_bwd")
+    L.rastk_check(L.rastk().foho_rastk_blend_bwd(*head, _p(go), *[_p(g) for g in grads], _stream(dists.device)), "foho_rastk_blend_bwd")
     return tuple(grads)
 
 
@@ -321,7 +319,7 @@ def _render_k_head(verts_ndc, faces, H, W, K, blur_radius, face_attr, sigma, gam
     V, F = keep[0].shape[0], keep[1].shape[0]
     rflags = L.RASTK_CULL_BACKFACES if cull_backfaces else 0
     bflags = (L.RASTK_BLEND_UNIT_BARY if unit_bary else 0) | (L.RASTK_BLEND_ALPHA_ONLY if alpha_only else 0)
-    head = [L._p(keep[0]), L._p(keep[1]), V, F, H, W, K, float(blur_radius), rflags, L._p(keep[2]), D, float(sigma), float(gamma),
+    head = [_p(keep[0]), _p(keep[1]), V, F, H, W, K, float(blur_radius), rflags, _p(keep[2]), D, float(sigma), float(gamma),
             float(znear), float(zfar), bg, bflags]
     return (V, F, H, W, K, D), head, keep
 
@@ -341,19 +339,10 @@ def render_k_fwd(verts_ndc, faces, H, W, K, blur_radius, face_attr, sigma, gamma
     out = torch.empty((H, W) if alpha_only else (H, W, D + 1), device=dev)
     cn = torch.empty(H, W, dtype=torch.int32, device=dev)
     ov = torch.zeros(1, dtype=torch.int32, device=dev)
-    retried = False
-    while True:
-        nws = lib.foho_rastk_workspace_bytes(V, F, H, W, K, cap)
-        if nws == 0:
-            raise L.FohoError(f"render_k_fwd: no workspace size for V={V} F={F} H={H} W={W} K={K} list_cap={cap}")
-        ws = torch.empty(nws, dtype=torch.uint8, device=dev)
-        L.rastk_check(lib.foho_rastk_render_fwd(*head, P(out.data_ptr()), P(cn.data_ptr()), P(ov.data_ptr()), cap, P(ws.data_ptr()), nws,
-                                                _stream(out)), "foho_rastk_render_fwd")
-        if not (int(ov.item()) & L.RASTK_OVER_LIST):      # one host read per call: the list size is data dependent
-            break
-        if retried:
-            raise L.FohoError("render_k_fwd: the tile lists overflowed again at the size the first pass reported")
-        cap, retried = int(ws[:8].view(torch.int64).item()), True
+
+    def launch(cap, ws):
+        L.rastk_check(lib.foho_rastk_render_fwd(*head, _p(out), _p(cn), _p(ov), cap, _p(ws), ws.numel(), _stream(dev)), "foho_rastk_render_fwd")
+    ws, cap, retried = _with_tile_lists("render_k_fwd", (V, F, H, W, K), cap, ov, launch)
     return dict(out=out, counts=cn, workspace=ws, list_cap=cap, retried=retried)
 
 
@@ -375,8 +364,8 @@ def render_k_bwd(verts_ndc, faces, H, W, K, blur_radius, face_attr, sigma, gamma
     gv = torch.zeros(V, 3, device=dev) if need[0] else None
     ga = torch.zeros(F, 3, D, device=dev) if need[1] and not alpha_only else None
     if gv is not None or ga is not None:
-        L.rastk_check(lib.foho_rastk_render_bwd(*head, P(go.data_ptr()), L._p(gv), L._p(ga), int(list_cap), P(workspace.data_ptr()),
-                                                workspace.numel(), _stream(go)), "foho_rastk_render_bwd")
+        L.rastk_check(lib.foho_rastk_render_bwd(*head, _p(go), _p(gv), _p(ga), int(list_cap), _p(workspace), workspace.numel(), _stream(dev)),
+                      "foho_rastk_render_bwd")
     return gv, ga
 
 
@@ -425,8 +414,7 @@ def knn1(p1, p2):
     a, b = _f32(p1), _f32(p2)
     d2 = torch.empty(a.shape[0], device=a.device)
     idx = torch.empty(a.shape[0], dtype=torch.int64, device=a.device)
-    L.check(lib.foho_knn1_fwd(P(a.data_ptr()), a.shape[0], P(b.data_ptr()), b.shape[0], P(d2.data_ptr()), P(idx.data_ptr()),
-                              _stream(a)), "foho_knn1_fwd")
+    L.check(lib.foho_knn1_fwd(_p(a), a.shape[0], _p(b), b.shape[0], _p(d2), _p(idx), _stream(a.device)), "foho_knn1_fwd")
     return d2, idx
 
 
@@ -437,8 +425,8 @@ def point_mesh_dist(verts, faces, pts):
     v, f, p = _f32(verts), faces.detach().to(torch.int32).contiguous(), _f32(pts)
     d2 = torch.empty(p.shape[0], device=p.device)
     fi = torch.empty(p.shape[0], dtype=torch.int64, device=p.device)
-    L.check(lib.foho_point_mesh_dist(P(v.data_ptr()), P(f.data_ptr()), v.shape[0], f.shape[0], P(p.data_ptr()), p.shape[0],
-                                     P(d2.data_ptr()), P(fi.data_ptr()), _stream(v)), "foho_point_mesh_dist")
+    L.check(lib.foho_point_mesh_dist(_p(v), _p(f), v.shape[0], f.shape[0], _p(p), p.shape[0], _p(d2), _p(fi), _stream(v.device)),
+            "foho_point_mesh_dist")
     return d2, fi
 
 
@@ -448,8 +436,7 @@ def inside_points(verts, faces, pts):
     lib = L.lib()
     v, f, p = _f32(verts), faces.detach().to(torch.int32).contiguous(), _f32(pts)
     out = torch.empty(p.shape[0], dtype=torch.uint8, device=p.device)
-    L.check(lib.foho_inside_points(P(v.data_ptr()), P(f.data_ptr()), v.shape[0], f.shape[0], P(p.data_ptr()), p.shape[0],
-                                   P(out.data_ptr()), _stream(v)), "foho_inside_points")
+    L.check(lib.foho_inside_points(_p(v), _p(f), v.shape[0], f.shape[0], _p(p), p.shape[0], _p(out), _stream(v.device)), "foho_inside_points")
     return out.bool()
 
 
@@ -474,7 +461,7 @@ class LbsModel:
         assert self.J_regressor.shape == (16, self.V) and self.lbs_weights.shape == (self.V, 16)
 
     def _args(self):
-        return [P(x.data_ptr()) for x in (self.v_template, self.shapedirs, self.posedirs, self.J_regressor,
+        return [_p(x) for x in (self.v_template, self.shapedirs, self.posedirs, self.J_regressor,
                                           self.lbs_weights, self.parents)] + [self.V]
 
 
@@ -484,13 +471,12 @@ class _LbsFn(torch.autograd.Function):
         lib = L.lib()
         B = betas.shape[0]
         b, r = _f32(betas), _f32(rot).reshape(B, 16, 3, 3)
-        lib.foho_lbs_workspace_bytes.restype = ctypes.c_size_t
         nws = lib.foho_lbs_workspace_bytes(B, model.V)
         ws = torch.empty(nws, dtype=torch.uint8, device=b.device)
         verts = torch.empty(B, model.V, 3, device=b.device)
         joints = torch.empty(B, 16, 3, device=b.device)
-        L.check(lib.foho_lbs_fwd(*model._args(), P(b.data_ptr()), P(r.data_ptr()), B, int(use_mfma), P(verts.data_ptr()),
-                                 P(joints.data_ptr()), P(ws.data_ptr()), ctypes.c_size_t(nws), _stream(b)), "foho_lbs_fwd")
+        L.check(lib.foho_lbs_fwd(*model._args(), _p(b), _p(r), B, int(use_mfma), _p(verts), _p(joints), _p(ws), nws, _stream(b.device)),
+                "foho_lbs_fwd")
         ctx.model, ctx.ws, ctx.nws, ctx.B = model, ws, nws, B
         ctx.save_for_backward(r)
         return verts, joints
@@ -504,8 +490,7 @@ class _LbsFn(torch.autograd.Function):
         gj = _f32(g_joints) if g_joints is not None else None
         gb = torch.empty(B, 10, device=r.device)
         gr = torch.empty(B, 16, 3, 3, device=r.device)
-        L.check(lib.foho_lbs_bwd(*model._args(), P(r.data_ptr()), B, P(gv.data_ptr()), P(gj.data_ptr()) if gj is not None else None,
-                                 P(gb.data_ptr()), P(gr.data_ptr()), P(ctx.ws.data_ptr()), ctypes.c_size_t(ctx.nws), _stream(r)),
+        L.check(lib.foho_lbs_bwd(*model._args(), _p(r), B, _p(gv), _p(gj), _p(gb), _p(gr), _p(ctx.ws), ctx.nws, _stream(r.device)),
                 "foho_lbs_bwd")
         return gb, gr, None, None
 
@@ -537,22 +522,20 @@ def icp_points_multi(start_points, target_points, n_iter, n_outliers=0, fixed_sc
             raise L.FohoError("icp_points_multi: target_faces must be (F,3)")
         if int(tf.min()) < 0 or int(tf.max()) >= M:
             raise L.FohoError("icp_points_multi: target face index out of range")
-        lib.foho_icp_surface_workspace_bytes.restype = ctypes.c_size_t
         nws = lib.foho_icp_surface_workspace_bytes(S, N, tf.shape[0])
     else:
-        lib.foho_icp_batch_workspace_bytes.restype = ctypes.c_size_t
         nws = lib.foho_icp_batch_workspace_bytes(S, N, M)
     ws = torch.empty(max(nws, 1), dtype=torch.uint8, device=device)
     T = torch.zeros(S, 16, dtype=torch.float64, device=device)
     cost = torch.zeros(S, dtype=torch.float64, device=device)
     hist = torch.zeros(S, max(n_iter, 1), dtype=torch.float64, device=device)
-    tail = (int(n_iter), int(n_outliers), int(bool(fixed_scale)), ctypes.c_double(min_scale), ctypes.c_double(max_scale),
-            P(T.data_ptr()), P(cost.data_ptr()), P(hist.data_ptr()), P(ws.data_ptr()), ctypes.c_size_t(nws), _stream(src))
+    tail = (int(n_iter), int(n_outliers), int(bool(fixed_scale)), min_scale, max_scale, _p(T), _p(cost), _p(hist), _p(ws), nws,
+            _stream(src.device))
     if tf is not None:
-        L.check(lib.foho_icp_run_surface(P(src.data_ptr()), S, N, P(tgt.data_ptr()), M, P(tf.data_ptr()), int(tf.shape[0]), *tail),
+        L.check(lib.foho_icp_run_surface(_p(src), S, N, _p(tgt), M, _p(tf), int(tf.shape[0]), *tail),
                 "foho_icp_run_surface")
     else:
-        L.check(lib.foho_icp_run_batch(P(src.data_ptr()), S, N, P(tgt.data_ptr()), M, *tail), "foho_icp_run_batch")
+        L.check(lib.foho_icp_run_batch(_p(src), S, N, _p(tgt), M, *tail), "foho_icp_run_batch")
     out = (T.cpu().numpy().reshape(S, 4, 4), cost.cpu().numpy())      # the copies synchronise
     return out + (hist.cpu().numpy()[:, :n_iter],) if return_history else out
 
@@ -579,7 +562,6 @@ class _FlexiFn(torch.autograd.Function):
         if xx.shape != (G ** 3, 3) or ss.numel() != G ** 3:
             raise L.FohoError(f"flexicubes: expected {(G ** 3, 3)} grid positions and {G ** 3} SDF values")
         dev = xx.device
-        lib.foho_flexi_workspace_bytes.restype = ctypes.c_size_t
         nws = lib.foho_flexi_workspace_bytes(res)
         ws = torch.empty(nws, dtype=torch.uint8, device=dev)
         counts = torch.zeros(3, dtype=torch.int32, device=dev)
@@ -587,9 +569,8 @@ class _FlexiFn(torch.autograd.Function):
             verts = torch.empty(verts_cap, 3, device=dev)
             faces = torch.empty(faces_cap, 3, dtype=torch.int64, device=dev)
             ldev = torch.empty(verts_cap, device=dev)
-            L.check(lib.foho_flexi_fwd(P(xx.data_ptr()), P(ss.data_ptr()), res, P(verts.data_ptr()), verts_cap,
-                                       P(faces.data_ptr()), faces_cap, P(ldev.data_ptr()), P(counts.data_ptr()),
-                                       P(ws.data_ptr()), ctypes.c_size_t(nws), _stream(xx)), "foho_flexi_fwd")
+            L.check(lib.foho_flexi_fwd(_p(xx), _p(ss), res, _p(verts), verts_cap, _p(faces), faces_cap, _p(ldev), _p(counts), _p(ws), nws,
+                                       _stream(dev)), "foho_flexi_fwd")
             nv, nf, over = counts.tolist()           # the output sizes are data dependent: one host sync per extraction
             if not over:
                 break
@@ -609,9 +590,8 @@ class _FlexiFn(torch.autograd.Function):
         g = _f32(g_verts)
         gs = torch.zeros_like(ss)
         gx = torch.zeros_like(xx) if ctx.need_x else None
-        L.check(lib.foho_flexi_bwd(P(xx.data_ptr()), P(ss.data_ptr()), ctx.res, P(g.data_ptr()), ctx.nv, P(gs.data_ptr()),
-                                   P(gx.data_ptr()) if gx is not None else None, P(ctx.ws.data_ptr()),
-                                   ctypes.c_size_t(ctx.ws.numel()), _stream(xx)), "foho_flexi_bwd")
+        L.check(lib.foho_flexi_bwd(_p(xx), _p(ss), ctx.res, _p(g), ctx.nv, _p(gs), _p(gx), _p(ctx.ws), ctx.ws.numel(), _stream(xx.device)),
+                "foho_flexi_bwd")
         # gradients in the shape and dtype the caller's tensors have (a (G,G,G) or half-precision SDF is a legal input)
         gs = gs.view(ctx.s_meta[0]).to(ctx.s_meta[1])
         if gx is not None:

@@ -38,7 +38,6 @@ def _workspace(lib, dev, M, Lk, H):
     key = (dev.index, M, Lk, H)
     ws = _workspaces.get(key)
     if ws is None:
-        lib.foho_sdpa_workspace_bytes.restype = ctypes.c_size_t
         n = int(lib.foho_sdpa_workspace_bytes(M, Lk, H))
         if n == 0:
             raise L.FohoError(f"foho_sdpa: shape (M={M}, L={Lk}, heads={H}) is outside what the kernels take")
@@ -94,8 +93,8 @@ class _HipSdpaFn(torch.autograd.Function):
         lse = torch.empty(B, H, M, dtype=torch.float32, device=q.device) if ctx.route == "torch" else None
         ws = _workspace(lib, q.device, M, Lk, H)
         d = _desc(q, k)
-        rc = lib.foho_sdpa_fwd(ctypes.byref(d), L.vp(q.data_ptr()), L.vp(k.data_ptr()), L.vp(v.data_ptr()), L.vp(out.data_ptr()), L.vp(nlse.data_ptr()),
-                               L.vp(lse.data_ptr()) if lse is not None else None, L.vp(ws.data_ptr()), ctypes.c_size_t(ws.numel()), L._stream(q.device))
+        rc = lib.foho_sdpa_fwd(ctypes.byref(d), L._p(q), L._p(k), L._p(v), L._p(out), L._p(nlse), L._p(lse), L._p(ws), ws.numel(),
+                               L._stream(q.device))
         L.geo_check(rc, "foho_sdpa_fwd")
         if lse is not None:
             ctx.save_for_backward(q, k, v, out, nlse, lse)
@@ -130,9 +129,8 @@ class _HipSdpaFn(torch.autograd.Function):
         gv = torch.empty(B, Lk, W, dtype=torch.float16, device=g.device)
         ws = _workspace(lib, q.device, M, Lk, H)
         d = _desc(q, k)
-        rc = lib.foho_sdpa_bwd(ctypes.byref(d), L.vp(q.data_ptr()), L.vp(k.data_ptr()), L.vp(v.data_ptr()), L.vp(out.data_ptr()), L.vp(nlse.data_ptr()),
-                               L.vp(go.data_ptr()), L.vp(gq.data_ptr()), L.vp(gk.data_ptr()), L.vp(gv.data_ptr()), L.vp(ws.data_ptr()),
-                               ctypes.c_size_t(ws.numel()), L._stream(g.device))
+        rc = lib.foho_sdpa_bwd(ctypes.byref(d), L._p(q), L._p(k), L._p(v), L._p(out), L._p(nlse), L._p(go), L._p(gq), L._p(gk), L._p(gv),
+                               L._p(ws), ws.numel(), L._stream(g.device))
         L.geo_check(rc, "foho_sdpa_bwd")
         return gq.view(B, M, H, 64).transpose(1, 2), gk.view(B, Lk, H, 64).transpose(1, 2), gv.view(B, Lk, H, 64).transpose(1, 2)
 

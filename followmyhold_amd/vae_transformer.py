@@ -96,7 +96,6 @@ def _fold(ln, lin, dev, perm=None):
 class HipVaeTransformer:
     def __init__(self, blocks, device="cuda"):
         self.lib = L.lib()
-        self.lib.foho_vae_abi_size.restype = ctypes.c_int64
         mine = ctypes.sizeof(FohoVaeLayer) * 1000 + ctypes.sizeof(FohoVaeDesc)
         if int(self.lib.foho_vae_abi_size()) != mine:
             raise L.FohoError(f"HipVaeTransformer: libfoho_hip.so's foho_vae structs ({int(self.lib.foho_vae_abi_size())}) differ from this binding's ({mine}): rebuild")
@@ -142,9 +141,6 @@ class HipVaeTransformer:
             y.eps1, y.eps2, y.qk_norm = eps1.pop(), float(p["ln2"].eps), int(qn is not None)
         self.zeros = torch.zeros(max(F, 3 * W), dtype=torch.float32, device=dev)
         self._ws = {}                     # (batch, tokens) -> workspace tensor (stream-ordered reuse)
-        for fn in (self.lib.foho_vae_workspace_bytes, self.lib.foho_vae_saved_bytes):
-            fn.restype = ctypes.c_size_t
-            fn.argtypes = [ctypes.POINTER(FohoVaeDesc)]
         self.flags = 0                    # foho_vae_desc.flags (A/B switches; 0 = the product path)
         self.calls = 0                    # forwards served (pipeline diagnostics: was the HIP route taken?)
         d = self._desc(1, 128)
@@ -193,10 +189,9 @@ class HipVaeTransformer:
         if keep:
             saved = torch.empty(int(self.lib.foho_vae_saved_bytes(ctypes.byref(d))), dtype=torch.uint8, device=self.device)
         out = torch.empty_like(x)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        L.geo_check(self.lib.foho_vae_fwd(ctypes.byref(d), L.vp(x.data_ptr()), L.vp(out.data_ptr()), L.vp(ws.data_ptr()), ctypes.c_size_t(ws.numel()),
-                                          L.vp(saved.data_ptr()) if saved is not None else None, ctypes.c_size_t(saved.numel() if saved is not None else 0),
-                                          L.vp(stream)), "foho_vae_fwd")
+        stream = L._stream(self.device)
+        L.geo_check(self.lib.foho_vae_fwd(ctypes.byref(d), L._p(x), L._p(out), L._p(ws), ws.numel(), L._p(saved),
+                                          saved.numel() if saved is not None else 0, stream), "foho_vae_fwd")
         self.calls += 1
         return out, saved
 
@@ -205,9 +200,9 @@ class HipVaeTransformer:
         d = self._desc(shape[0], shape[1])
         ws = self._workspace(d)
         gx = torch.empty(shape, dtype=torch.float16, device=self.device)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        L.geo_check(self.lib.foho_vae_bwd(ctypes.byref(d), L.vp(g.data_ptr()), L.vp(gx.data_ptr()), L.vp(ws.data_ptr()), ctypes.c_size_t(ws.numel()),
-                                          L.vp(saved.data_ptr()), ctypes.c_size_t(saved.numel()), L.vp(stream)), "foho_vae_bwd")
+        stream = L._stream(self.device)
+        L.geo_check(self.lib.foho_vae_bwd(ctypes.byref(d), L._p(g), L._p(gx), L._p(ws), ws.numel(), L._p(saved), saved.numel(), stream),
+                    "foho_vae_bwd")
         return gx
 
     def __call__(self, x):

@@ -7,7 +7,6 @@ import torch
 from followmyhold_amd import _lib as L
 
 lib = L.lib()
-lib.foho_geo_gemm.restype = ctypes.c_int
 P = lambda t: ctypes.c_void_p(t.data_ptr())
 st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 

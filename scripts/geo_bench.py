@@ -34,7 +34,6 @@ if "--fb" in sys.argv:
     sys.exit(0)
 if "--parts" in sys.argv:
     lib = L.lib()
-    lib.foho_geo_last_error.restype = ctypes.c_char_p
     P = lambda t: ctypes.c_void_p(t.data_ptr())
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     for M in (16384, 49152):

@@ -6,29 +6,38 @@ import re
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "followmyhold_amd", "csrc")
+HIP_HEADER = os.path.join(ROOT, "include", "foho_hip.h")
+# library -> (header, the number of prototypes it holds); the side libraries: followmyhold_amd/csrc/foho_<name>.h
+HEADERS = {"hip": (HIP_HEADER, 58), "vol": (os.path.join(CSRC, "foho_vol.h"), 10), "sflexi": (os.path.join(CSRC, "foho_sflexi.h"), 8),
+           "rastk": (os.path.join(CSRC, "foho_rastk.h"), 9)}
 
 
-def declared_functions():
-    names = []
-    for fn in sorted(os.listdir(os.path.join(ROOT, "include"))):
-        if not fn.endswith(".h"):
-            continue
-        src = open(os.path.join(ROOT, "include", fn)).read()
-        src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)            # strip comments
-        src = re.sub(r"//[^\n]*", "", src)
-        src = re.sub(r"typedef\s+struct\s*\{.*?\}\s*\w+\s*;", "", src, flags=re.S)
-        src = re.sub(r"typedef\s+enum\s*\{.*?\}\s*\w+\s*;", "", src, flags=re.S)
-        src = re.sub(r"enum\s*\{.*?\}\s*;", "", src, flags=re.S)
-        for m in re.finditer(r"\b(foho_\w+)\s*\(", src):
-            names.append(m.group(1))
-    return sorted(set(names))
+def prototypes(header):
+    """Every FOHO_*API prototype of a header as (name, return type, [parameter types]): `const` and the parameter names dropped,
+    a pointer or array written `base*` ("int32_t", "char*", "foho_dims*")."""
+    def ctype(decl, named):
+        words = re.sub(r"\bconst\b|\[\w*\]|\*", " ", decl).split()
+        return " ".join(words[:-1] if named else words) + ("*" if "*" in decl or "[" in decl else "")
+
+    src = re.sub(r"/\*.*?\*/", "", open(header).read(), flags=re.S)            # strip comments
+    src = re.sub(r"//[^\n]*", "", src)
+    out = []
+    for ret, name, params in re.findall(r"\bFOHO_\w*API\s+([\w\s*]+?)\b(foho_\w+)\s*\(([^()]*)\)\s*;", src):
+        params = [] if params.strip() == "void" else [ctype(p, True) for p in params.split(",")]
+        out.append((name, ctype(ret, False), params))
+    return out
+
+
+def declared_functions(header=HIP_HEADER):
+    return sorted(name for name, _, _ in prototypes(header))
 
 
 @pytest.fixture(scope="module")
 def lib():
     from followmyhold_amd import _lib
     _lib.build()
-    return ctypes.CDLL(_lib.SO_PATH)
+    return _lib.lib()
 
 
 def test_header_declares_the_expected_entry_points():
@@ -37,6 +46,52 @@ def test_header_declares_the_expected_entry_points():
                  "foho_version", "foho_step_run_profiled", "foho_geo_decode_fwd", "foho_vae_fwd", "foho_vae_bwd", "foho_sdpa_fwd", "foho_icp_run"]:
         assert must in names
     assert len(names) == 58, len(names)
+
+
+@pytest.mark.parametrize("name", sorted(HEADERS))
+def test_signature_tables_are_the_headers(name):
+    """The {function: (restype, argtypes)} table of each library against the prototypes of its header: the same functions, and per
+    function the ctypes type of the return value and of every parameter."""
+    from followmyhold_amd import _lib as L, sparse_flexi, volume
+    from followmyhold_amd.geo_decode import FohoGeoWeights
+    from followmyhold_amd.sdpa import FohoSdpaDesc
+    from followmyhold_amd.vae_transformer import FohoVaeDesc
+    scalars = {"int": ctypes.c_int32, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t,
+               "float": ctypes.c_float, "double": ctypes.c_double, "char*": ctypes.c_char_p}
+    mirrors = {"foho_dims*": L.FohoDims, "foho_step_desc*": L.FohoStepDesc, "foho_step_cfg*": L.FohoStepCfg,
+               "foho_geo_weights*": FohoGeoWeights, "foho_sdpa_desc*": FohoSdpaDesc, "foho_vae_desc*": FohoVaeDesc}
+    header, count = HEADERS[name]
+    protos = prototypes(header)
+    assert len(protos) == count == len({p[0] for p in protos}), [p[0] for p in protos]        # a skipped prototype fails here
+    table = {"hip": L._SIGNATURES, "vol": volume._SIGNATURES, "sflexi": sparse_flexi._SIGNATURES, "rastk": L._RASTK_SIGNATURES}[name]
+    typed_by_loader = () if name == "hip" else (f"foho_{name}_version", f"foho_{name}_last_error")
+    assert set(table) == {p[0] for p in protos} - set(typed_by_loader)
+    for fn, ret, params in protos:
+        if fn in typed_by_loader:
+            continue
+        restype, argtypes = table[fn]
+        assert restype is scalars[ret], (fn, ret, restype)
+        assert len(argtypes) == len(params), (fn, params, argtypes)
+        for i, (c, t) in enumerate(zip(params, argtypes)):
+            if c.endswith("*"):
+                assert t is ctypes.c_void_p or (c in mirrors and t is ctypes.POINTER(mirrors[c])), (fn, i, c, t)
+            else:
+                assert t is scalars[c], (fn, i, c, t)
+
+
+def test_size_queries_beyond_32_bits_come_back_exact():
+    """The hazard the tables remove: a size_t that a call without a declared restype would return as a C int.  No type is set here."""
+    from followmyhold_amd import _lib as L
+    from followmyhold_amd.geo_decode import FohoGeoWeights
+    L.build()
+    lib = L.lib()
+    assert lib.foho_flexi_workspace_bytes(384) == 1_879_652_864
+    w = FohoGeoWeights()
+    w.width, w.heads, w.n_latents, w.hidden, w.n_freqs = 1024, 16, 3072, 4096, 8
+    for field, typ in FohoGeoWeights._fields_:
+        if typ is L.vp:
+            setattr(w, field, 1)
+    assert lib.foho_geo_saved_bytes(ctypes.byref(w), 16384, 65 ** 3) == 5_151_653_888 > 1 << 32
 
 
 def test_every_declared_symbol_is_exported(lib):
@@ -57,35 +112,26 @@ def test_nothing_but_the_declared_entry_points_is_exported():
 
 def test_host_only_queries_work_without_a_gpu(lib):
     from followmyhold_amd import _lib as L
-    lib.foho_version.restype = ctypes.c_int
     assert lib.foho_version() >= 100
     d = L.FohoDims()
     d.B, d.H, d.W, d.Vtot, d.Ftot, d.Vmax, d.Fmax, d.Vh_max, d.Vo_max = 2, 512, 512, 22040, 44064, 11020, 22032, 778, 10242
     d.grid_res, d.frac_cap, d.n_renders = 64, 1 << 18, 2
-    lib.foho_step_workspace_bytes.restype = ctypes.c_size_t
     n = lib.foho_step_workspace_bytes(ctypes.byref(d))
     assert 10_000_000 < n < 2_000_000_000
-    lib.foho_step_workspace_region.restype = ctypes.c_int64
     nb = ctypes.c_int64(0)
     off = lib.foho_step_workspace_region(ctypes.byref(d), L.WS_REGIONS.index("p2f"), ctypes.byref(nb))
     assert off >= 0 and nb.value == 2 * 2 * 512 * 512 * 4 and off + nb.value <= n
     assert lib.foho_step_workspace_region(ctypes.byref(d), 999, ctypes.byref(nb)) == -1
     # argument validation happens before any launch
-    lib.foho_step_run.restype = ctypes.c_int
     assert lib.foho_step_run(None, None, 0, None) == -1
-    lib.foho_last_error.restype = ctypes.c_char_p
     assert b"null" in lib.foho_last_error()
     # size queries and argument checks of the other entry points
     for fn, args, lo in [("foho_flexi_workspace_bytes", (64,), 1_000_000), ("foho_topology_workspace_bytes", (11020,), 50_000),
                          ("foho_raster_workspace_bytes", (11020, 22032, 512, 512), 1_000_000), ("foho_icp_workspace_bytes", (5000, 10000), 1)]:
-        f = getattr(lib, fn)
-        f.restype = ctypes.c_size_t
-        assert f(*args) >= lo, fn
+        assert getattr(lib, fn)(*args) >= lo, fn
     assert lib.foho_flexi_workspace_bytes(0) == 0 and lib.foho_topology_workspace_bytes(0) == 0
-    lib.foho_flexi_fwd.restype = ctypes.c_int
     assert lib.foho_flexi_fwd(None, None, 64, None, 0, None, 0, None, None, None, ctypes.c_size_t(0), None) == -1
     assert b"foho_flexi_fwd" in lib.foho_last_error()
-    lib.foho_topology_tables.restype = ctypes.c_int
     assert lib.foho_topology_tables(None, 10, 10, None, None, None, None, None, None, ctypes.c_size_t(0), None) == -1
 
 
@@ -99,7 +145,6 @@ def test_struct_layouts_match_the_header(lib):
     assert ctypes.sizeof(L.FohoStepDesc) == 64 + 21 * 8 + 8 + 8          # hand_order_valid + hand_faces_per_block
     # ... and the library this binding loads was built from the same layout (the check _lib.lib() makes at load time)
     sizes = (ctypes.c_int64 * 5)()
-    lib.foho_abi_sizes.restype = ctypes.c_int
     assert lib.foho_abi_sizes(sizes) == lib.foho_version() == L.ABI_VERSION
     assert list(sizes) == [ctypes.sizeof(t) for t in (L.FohoImage, L.FohoDims, L.FohoRenderCfg, L.FohoStepCfg, L.FohoStepDesc)]
 
@@ -119,7 +164,6 @@ def _layout_queries():
     from followmyhold_amd.vae_transformer import FohoVaeDesc, FohoVaeLayer
     L.build()
     lib = L.lib()
-    sz, i32, i64 = ctypes.c_size_t, ctypes.c_int32, ctypes.c_int64
     got = {}
 
     def dims(B, H, W, Vh, Vo, Fh, Fo, grid_res, frac_cap):
@@ -131,20 +175,18 @@ def _layout_queries():
     for tag, d in (("b2_512", dims(2, 512, 512, 778, 10242, 1552, 20480, 64, 1 << 18)), ("b1_64", dims(1, 64, 64, 778, 642, 1538, 1280, 16, 1 << 14))):
         got[f"step/{tag}"] = lib.foho_step_workspace_bytes(ctypes.byref(d))
         for i, name in enumerate(L.WS_REGIONS):
-            nb = i64(0)
+            nb = ctypes.c_int64(0)
             got[f"step/{tag}/{name}"] = (lib.foho_step_workspace_region(ctypes.byref(d), i, ctypes.byref(nb)), nb.value)
 
-    def q(fn, argtypes, *args):
-        f = getattr(lib, fn)
-        f.restype, f.argtypes = sz, argtypes
-        return f(*args)
+    def q(fn, *args):
+        return getattr(lib, fn)(*args)
 
     for res in (1, 8, 64, 384):
-        got[f"flexi/{res}"] = q("foho_flexi_workspace_bytes", [i32], res)
-    got["topology/11020"] = q("foho_topology_workspace_bytes", [i32], 11020)
-    got["raster/11020,22032,512,512"] = q("foho_raster_workspace_bytes", [i32] * 4, 11020, 22032, 512, 512)
-    got["icp/5000,10000"] = q("foho_icp_workspace_bytes", [i32] * 2, 5000, 10000)
-    got["sdpa/3072,3072,16"] = q("foho_sdpa_workspace_bytes", [i32] * 3, 3072, 3072, 16)
+        got[f"flexi/{res}"] = q("foho_flexi_workspace_bytes", res)
+    got["topology/11020"] = q("foho_topology_workspace_bytes", 11020)
+    got["raster/11020,22032,512,512"] = q("foho_raster_workspace_bytes", 11020, 22032, 512, 512)
+    got["icp/5000,10000"] = q("foho_icp_workspace_bytes", 5000, 10000)
+    got["sdpa/3072,3072,16"] = q("foho_sdpa_workspace_bytes", 3072, 3072, 16)
     S = sparse_flexi.lib()
     for res in (1, 13, 384):
         got[f"sflexi_mark/{res}"] = S.foho_sflexi_mark_bytes(res)
@@ -159,10 +201,8 @@ def _layout_queries():
         for name, typ in FohoGeoWeights._fields_:
             if typ is L.vp:
                 setattr(w, name, 1)
-        P = ctypes.POINTER(FohoGeoWeights)
-        got[f"geo/{width}"] = (q("foho_geo_workspace_bytes", [P, i32], ctypes.byref(w), chunk),
-                               q("foho_geo_bwd_workspace_bytes", [P, i32], ctypes.byref(w), chunk),
-                               q("foho_geo_saved_bytes", [P, i32, i64], ctypes.byref(w), chunk, n))
+        got[f"geo/{width}"] = (q("foho_geo_workspace_bytes", ctypes.byref(w), chunk), q("foho_geo_bwd_workspace_bytes", ctypes.byref(w), chunk),
+                               q("foho_geo_saved_bytes", ctypes.byref(w), chunk, n))
     for width, heads, hidden, n_layers, tokens in ((1024, 16, 4096, 16, 3072), (128, 2, 512, 2, 128)):
         layers = (FohoVaeLayer * n_layers)()
         for y in layers:
@@ -175,8 +215,7 @@ def _layout_queries():
         d.width, d.heads, d.hidden, d.n_layers, d.n_tokens, d.batch = width, heads, hidden, n_layers, tokens, 1
         d.layers = ctypes.cast(layers, ctypes.POINTER(FohoVaeLayer))
         d.zeros = 1
-        P = ctypes.POINTER(FohoVaeDesc)
-        got[f"vae/{width}"] = (q("foho_vae_workspace_bytes", [P], ctypes.byref(d)), q("foho_vae_saved_bytes", [P], ctypes.byref(d)))
+        got[f"vae/{width}"] = (q("foho_vae_workspace_bytes", ctypes.byref(d)), q("foho_vae_saved_bytes", ctypes.byref(d)))
     return got
 
 

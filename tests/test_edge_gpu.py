@@ -267,7 +267,6 @@ def _raster_fwd(ndc, faces, H, W, blur):
     from followmyhold_amd import _lib as L
     lib = L.lib()
     dv, df = torch.from_numpy(ndc).cuda(), torch.from_numpy(faces.astype(np.int32)).cuda()
-    lib.foho_raster_workspace_bytes.restype = ctypes.c_size_t
     nws = lib.foho_raster_workspace_bytes(len(ndc), len(faces), H, W)
     ws = torch.zeros(nws, dtype=torch.uint8, device="cuda")
     p2f = torch.empty(H * W, dtype=torch.int64, device="cuda")

@@ -16,7 +16,6 @@ gpu = pytest.mark.gpu
 def _lib():
     from followmyhold_amd import _lib as L
     lib = L.lib()
-    lib.foho_geo_last_error.restype = ctypes.c_char_p
     return L, lib
 
 
@@ -27,8 +26,6 @@ def _p(t):
 def test_geo_workspace_query_and_argument_checks_run_without_a_gpu():
     from followmyhold_amd.geo_decode import FohoGeoWeights
     L, lib = _lib()
-    lib.foho_geo_workspace_bytes.restype = ctypes.c_size_t
-    lib.foho_geo_workspace_bytes.argtypes = [ctypes.POINTER(FohoGeoWeights), ctypes.c_int32]
     w = FohoGeoWeights()
     w.width, w.heads, w.n_latents, w.hidden, w.n_freqs = 1024, 16, 3072, 4096, 8
     for name, typ in FohoGeoWeights._fields_:
@@ -44,22 +41,16 @@ def test_geo_workspace_query_and_argument_checks_run_without_a_gpu():
     assert lib.foho_geo_workspace_bytes(ctypes.byref(w), 16384) == 0 and b"head dimension" in lib.foho_geo_last_error()
     w.heads, w.n_latents = 16, 100
     assert lib.foho_geo_workspace_bytes(ctypes.byref(w), 16384) == 0 and b"n_latents" in lib.foho_geo_last_error()
-    lib.foho_geo_decode_fwd.restype = ctypes.c_int
     assert lib.foho_geo_decode_fwd(None, None, ctypes.c_int64(0), None, 0, None, ctypes.c_size_t(0), None) == -1
     # the backward's sizes: 18.1 KB of kept activations per query row (rounded up to whole row blocks), a workspace that holds one
     # row block's scratch + the partial sums of the K / V gradient; argument errors come back as codes, not as faults
     w.n_latents = 3072
-    for fn in (lib.foho_geo_bwd_workspace_bytes, lib.foho_geo_saved_bytes):
-        fn.restype = ctypes.c_size_t
-    lib.foho_geo_bwd_workspace_bytes.argtypes = [ctypes.POINTER(FohoGeoWeights), ctypes.c_int32]
-    lib.foho_geo_saved_bytes.argtypes = [ctypes.POINTER(FohoGeoWeights), ctypes.c_int32, ctypes.c_int64]
     per_row_saved = 2 * (5 * 1024 + 4096) + 16 * 4
     n = lib.foho_geo_saved_bytes(ctypes.byref(w), 16384, 65 ** 3)
     assert 17 * 16384 * per_row_saved <= n <= 17 * 16384 * (per_row_saved + 64) + 17 * 8192
     nb = lib.foho_geo_bwd_workspace_bytes(ctypes.byref(w), 16384)
     part = 3072 * 2048 * 4
     assert nb >= 16384 * 2 * (64 + 7 * 1024 + 2 * 4096) + part and (nb - 16384 * 2 * (64 + 9 * 1024 + 2 * 4096)) % part < part
-    lib.foho_geo_decode_bwd.restype = ctypes.c_int
     assert lib.foho_geo_decode_bwd(None, None, ctypes.c_int64(0), None, None, 0, None, ctypes.c_size_t(0), None, ctypes.c_size_t(0), None,
                                    ctypes.c_size_t(0), None) == -1
     w.n_latents = 3072 + 64              # fine for the forward, not for the backward's 128-key blocks
@@ -80,7 +71,6 @@ def test_gemm_epilogues_against_torch(M, N, K, mode):
     R = torch.randn(M, N, generator=g).half().cuda() if mode == "resid" else None
     C = torch.full((M, N), float("nan"), dtype=torch.float16, device="cuda")
     scale = 0.18 if mode == "scale" else 1.0
-    lib.foho_geo_gemm.restype = ctypes.c_int
     rc = lib.foho_geo_gemm(_p(A), _p(W), _p(b), _p(R) if R is not None else None, _p(C), M, N, K, int(mode == "gelu"), ctypes.c_float(scale),
                            ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
     assert rc == 0, lib.foho_geo_last_error()
@@ -108,7 +98,6 @@ def test_gemm_kernel_variants_give_the_same_bits(M, N, K, resid):
     W = (torch.randn(N, K, generator=g) / math.sqrt(K)).half().cuda()
     b = torch.randn(N, generator=g).cuda()
     R = torch.randn(M, N, generator=g).half().cuda() if resid else None
-    lib.foho_geo_gemm.restype = ctypes.c_int
     outs = {}
     for flag in (0, 2, 4, 8, 16, 32, 64):
         C = torch.full((M, N), float("nan"), dtype=torch.float16, device="cuda")
@@ -143,7 +132,6 @@ def test_gemm128_rings_shorter_than_their_depth(M, N, K, resid):
     W = (torch.randn(N, K, generator=g) / math.sqrt(K)).half().cuda()
     b = torch.randn(N, generator=g).cuda()
     R = torch.randn(M, N, generator=g).half().cuda() if resid else None
-    lib.foho_geo_gemm.restype = ctypes.c_int
     outs = {}
     for flag in (2, 8, 32):
         C = torch.full((M, N), float("nan"), dtype=torch.float16, device="cuda")
@@ -176,7 +164,6 @@ def test_attention_against_torch(M, Lk, heads):
     kvh = kv.half().cuda()
     O = torch.full((M, W), float("nan"), dtype=torch.float16, device="cuda")
     vt = torch.empty(W * Lk, dtype=torch.float16, device="cuda")
-    lib.foho_geo_attention.restype = ctypes.c_int
     rc = lib.foho_geo_attention(_p(qs), _p(kvh), _p(vt), _p(O), M, Lk, heads, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
     assert rc == 0, lib.foho_geo_last_error()
     torch.cuda.synchronize()

@@ -12,11 +12,9 @@ gpu = pytest.mark.gpu
 def test_sdpa_argument_checks_run_without_a_gpu():
     from followmyhold_amd import _lib as L
     lib = L.lib()
-    lib.foho_sdpa_workspace_bytes.restype = ctypes.c_size_t
     assert lib.foho_sdpa_workspace_bytes(3072, 3072, 16) > 2 * 1024 * 3072 * 2
     assert lib.foho_sdpa_workspace_bytes(3072, 3000, 16) == 0            # keys not a multiple of 64
     assert lib.foho_sdpa_workspace_bytes(3072, 3072, 17) == 0
-    lib.foho_sdpa_fwd.restype = lib.foho_sdpa_bwd.restype = ctypes.c_int
     from followmyhold_amd import sdpa
     one = ctypes.c_void_p(1)
     d = sdpa.FohoSdpaDesc(64, 128, 2, 1, 64 * 128, 128, 64, 128 * 256, 256, 64)

@@ -81,7 +81,6 @@ def test_binding_validates_arguments_without_a_gpu():
 def test_workspace_is_monotone_and_a_tenth_of_the_dense_one():
     _make()
     L, H = SF.lib(), _lib.lib()
-    H.foho_flexi_workspace_bytes.restype = ctypes.c_size_t
     sizes = [L.foho_sflexi_workspace_bytes(384, c) for c in (0, 1, 1000, 100_000, 2_000_000, 20_000_000)]
     assert sizes[0] > 0 and all(a <= b for a, b in zip(sizes, sizes[1:])) and sizes[0] < sizes[-1]
     assert L.foho_sflexi_workspace_bytes(384, 2_000_000) <= H.foho_flexi_workspace_bytes(384) // 10
@@ -323,7 +322,6 @@ def _sparse_raw(ax, s, res, n_cubes, verts_cap, faces_cap, guard, want_ldev=True
 
 def _dense_raw(x, s, res, verts_cap, faces_cap, guard, want_ldev=True):
     H = _lib.lib()
-    H.foho_flexi_workspace_bytes.restype = ctypes.c_size_t
     nws = H.foho_flexi_workspace_bytes(res)
     ws = torch.empty(nws, dtype=torch.uint8, device="cuda")
     verts = torch.full((verts_cap * 3 + guard,), -7.5, device="cuda")

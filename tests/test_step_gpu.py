@@ -224,7 +224,6 @@ def test_standalone_raster_and_knn_ops():
     ref = clib.render_pass(ndc[torch.from_numpy(f)].numpy(), H, W, blur)
     dv = ndc.cuda()
     df = torch.from_numpy(f).int().cuda()
-    lib.foho_raster_workspace_bytes.restype = ctypes.c_size_t
     nws = lib.foho_raster_workspace_bytes(len(v), len(f), H, W)
     ws = torch.zeros(nws, dtype=torch.uint8, device="cuda")
     p2f = torch.empty(H * W, dtype=torch.int64, device="cuda")

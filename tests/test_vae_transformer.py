@@ -90,12 +90,7 @@ def test_vae_sizes_and_argument_checks_run_without_a_gpu():
     from followmyhold_amd import _lib as L
     from followmyhold_amd.vae_transformer import FohoVaeDesc, FohoVaeLayer
     lib = L.lib()
-    lib.foho_vae_abi_size.restype = ctypes.c_int64
     assert lib.foho_vae_abi_size() == ctypes.sizeof(FohoVaeLayer) * 1000 + ctypes.sizeof(FohoVaeDesc)
-    for fn in (lib.foho_vae_workspace_bytes, lib.foho_vae_saved_bytes):
-        fn.restype = ctypes.c_size_t
-        fn.argtypes = [ctypes.POINTER(FohoVaeDesc)]
-    lib.foho_geo_last_error.restype = ctypes.c_char_p
     layers = (FohoVaeLayer * 16)()
     for y in layers:
         for name, typ in FohoVaeLayer._fields_:
@@ -118,7 +113,6 @@ def test_vae_sizes_and_argument_checks_run_without_a_gpu():
     assert lib.foho_vae_workspace_bytes(ctypes.byref(d)) == 0 and b"head dimension" in lib.foho_geo_last_error()
     d.heads, d.n_tokens = 16, 3000
     assert lib.foho_vae_saved_bytes(ctypes.byref(d)) == 0 and b"n_tokens" in lib.foho_geo_last_error()
-    lib.foho_vae_fwd.restype = ctypes.c_int
     assert lib.foho_vae_fwd(None, None, None, None, ctypes.c_size_t(0), None, ctypes.c_size_t(0), None) == -1
 
 

@@ -3,7 +3,6 @@ surface only, with the dense path's mesh as the contract.  CPU: the library, its
 restatement (tests/vol_ref.py) on analytic fields.  GPU: decoder row independence (what the contract rests on), kernels against
 vol_ref index for index, mesh identity with the dense path, the work saved, and the pipeline switch."""
 import os
-import re
 import subprocess
 import sys
 
@@ -13,6 +12,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import vol_ref as V  # noqa: E402
+from test_cabi import declared_functions as _declared  # noqa: E402
 
 from followmyhold_amd import _lib, pipeline as PLN, standins, volume  # noqa: E402
 from followmyhold_amd.facade import generate_dense_grid_points  # noqa: E402
@@ -27,11 +27,6 @@ def _exported(path):
     out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
     names = sorted(l.split()[-1] for l in out.splitlines() if len(l.split()) >= 3 and l.split()[-2] in ("T", "t", "W", "V", "B", "D"))
     return [n for n in names if not n.startswith(("_init", "_fini", "__bss_start", "_edata", "_end", "__hip_"))]
-
-
-def _declared(path):
-    src = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(foho_vol_\w+)\s*\(", src)))
 
 
 # ---------------------------------------------------------------- analytic fields (numpy and torch, the same elementwise ops)
