@@ -909,7 +909,9 @@ __device__ __forceinline__ float other_half(float x) {
 // (results stayed accurate but differed from run to run).  The translation unit is built with -fno-honor-nans, which is
 // what keeps the compiler from putting a canonicalising v_max_f32 x, x in front of every operand.
 __device__ __forceinline__ float max3(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
-__device__ __forceinline__ float ex2(float x) { return __builtin_amdgcn_exp2f(x); }  // bare v_exp_f32: arguments are <= 6, underflow to 0 is what is wanted
+// bare v_exp_f32.  What it sees: a score minus the running max (<= RESCALE_THR in the forward; minus the final lse, <= ~0, in the two backward
+// kernels) and -up <= 0 of a LATER unit's rescale -- underflow to 0 is what is wanted.  Never the FIRST unit's -up: that one has no upper bound.
+__device__ __forceinline__ float ex2(float x) { return __builtin_amdgcn_exp2f(x); }
 
 __global__ __launch_bounds__(256, 2) void k_geo_attn(const h16* __restrict__ Q, int ldq, const h16* __restrict__ Kp, int ldk,
                                                      const h16* __restrict__ Vt, int L, h16* __restrict__ O, int ldo, int M,
@@ -1016,7 +1018,9 @@ __global__ __launch_bounds__(256, 2) void k_geo_attn(const h16* __restrict__ Q, 
         if (first || __any(tm > RESCALE_THR)) {
             tm = fmaxf(tm, other_half(tm));
             const float up = first ? tm : fmaxf(tm, 0.0f);
-            const float alpha = ex2(-up);
+            // the first unit has nothing to rescale (lsum and o are zero) and its maximum may lie anywhere: with the first 32 scores
+            // below -128, ex2(-up) is +inf and 0 * inf made the row NaN.  Only sc and negm take `up` there.
+            const float alpha = first ? 1.0f : ex2(-up);
             lsum[qb] *= alpha;
 #pragma unroll
             for (int r = 0; r < 16; r++) {

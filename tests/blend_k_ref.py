@@ -91,7 +91,8 @@ def torch_alpha(pix_to_face, dists, sigma, dtype):
 def route_with_grads(case, sigma, gamma, dtype, device, unit_bary=False):
     """dict over NAMES: the torch route's output and its gradients to zbuf, bary, dists and face_attr under case['grad_out'].
     With unit_bary the barycentrics carry no gradient (None)."""
-    leaves = {k: case[k].to(device).to(dtype).requires_grad_(True) for k in ("zbuf", "bary", "dists", "face_attr")}
+    # (detach(): on the CPU in float32 both .to() return the case's OWN tensor, and the cached case must not come to require grad)
+    leaves = {k: case[k].detach().to(device).to(dtype).requires_grad_(True) for k in ("zbuf", "bary", "dists", "face_attr")}
     planes = dict(pix_to_face=case["pix_to_face"].to(device), zbuf=leaves["zbuf"], bary=leaves["bary"], dists=leaves["dists"])
     out = torch_route(planes, leaves["face_attr"], case["background"], sigma, gamma, dtype, unit_bary)
     keys = [k for k in ("zbuf", "bary", "dists", "face_attr") if not (unit_bary and k == "bary")]
