@@ -447,8 +447,9 @@ def get_sdf_of_meshes(mesh1: Meshes, mesh2: Meshes, device, resolution=64):
 
 
 class FlexiCubes:
-    """kaolin.non_commercial.FlexiCubes as the pipeline uses it (pipelines.py:1142-1143, 1393, 1509): default weights, no
-    training mode -- Dual Marching Cubes on the regular grid, differentiable w.r.t. the SDF (libfoho_hip: k_flexi.inc)."""
+    """kaolin.non_commercial.FlexiCubes on the regular grid.  As the pipeline uses it (pipelines.py:1142-1143, 1393, 1509) -- default
+    weights, no training mode -- it is Dual Marching Cubes, differentiable w.r.t. the SDF (libfoho_hip: k_flexi.inc); with beta_fx12,
+    alpha_fx8, gamma_f or training=True it is the weighted operator (libfoho_wflexi: foho_wflexi.hip), differentiable w.r.t. those too."""
 
     _CORNERS = [(0, 0, 0), (1, 0, 0), (0, 1, 0), (1, 1, 0), (0, 0, 1), (1, 0, 1), (0, 1, 1), (1, 1, 1)]
 
@@ -466,9 +467,25 @@ class FlexiCubes:
         offs = torch.tensor([(cx * G + cy) * G + cz for cx, cy, cz in self._CORNERS], device=self.device)
         return verts, base[:, None] + offs[None, :]
 
+    WEIGHT_SCALE = 0.99
+    # kaolin's cube-edge order, as recalled from its cube_edges -- (0,1) (1,5) (4,5) (0,4) (2,3) (3,7) (6,7) (2,6) (2,0) (3,1) (7,5) (6,4)
+    # -- in this repository's edge ids: column k of beta_fx12 is the weight of edge KAOLIN_EDGE_TO_OURS[k].  PARITY UNPINNED.
+    KAOLIN_EDGE_TO_OURS = (0, 9, 2, 8, 1, 11, 3, 10, 4, 5, 7, 6)
+
     def __call__(self, x_nx3, s_n, cube_fx8, res, beta_fx12=None, alpha_fx8=None, gamma_f=None, training=False, **_):
-        if beta_fx12 is not None or alpha_fx8 is not None or gamma_f is not None or training:
-            raise NotImplementedError("only the default-weight call of pipelines.py:1393 / 1509 is implemented")
+        """Without weights and training: ops.flexicubes (libfoho_hip: k_flexi.inc).  Otherwise the raw weights are normalised as kaolin
+        does, in torch, so that autograd chains into them, and the call is ops.flexicubes_weighted (libfoho_wflexi: foho_wflexi.hip)."""
         if cube_fx8 is not None and cube_fx8.shape[0] != res ** 3:
             raise ValueError("cube_fx8 must be the regular grid of construct_voxel_grid(res)")
-        return ops.flexicubes(x_nx3, s_n, int(res))
+        if beta_fx12 is None and alpha_fx8 is None and gamma_f is None and not training:
+            return ops.flexicubes(x_nx3, s_n, int(res))
+        beta = alpha = gamma = None
+        if beta_fx12 is not None:
+            ours = torch.empty(12, dtype=torch.long)
+            ours[list(self.KAOLIN_EDGE_TO_OURS)] = torch.arange(12)          # our edge e is kaolin's column ours[e]
+            beta = (torch.tanh(beta_fx12) * self.WEIGHT_SCALE + 1)[:, ours.to(beta_fx12.device)]
+        if alpha_fx8 is not None:
+            alpha = torch.tanh(alpha_fx8) * self.WEIGHT_SCALE + 1
+        if gamma_f is not None:
+            gamma = torch.sigmoid(gamma_f) * self.WEIGHT_SCALE + 0.005
+        return ops.flexicubes_weighted(x_nx3, s_n, int(res), alpha=alpha, beta=beta, gamma=gamma, training=bool(training))
