@@ -17,12 +17,14 @@
 //   k_sf_emit       vertices per surface cube (positions from the tables), quads per (axis, surface cube), the four ring cubes
 //                   through rank()
 //   k_sf_bwd        dL/ds from dL/dvertices (foho_sflexi_bwd), on what the kernels above left: 8 threads per surface cube, the owner
-//                   of a grid point gathers its at most 24 terms in a fixed order and stores once -- no float atomics
-// Compiled with foho_step.hip's flags (-ffp-contract=off, correctly rounded division and sqrt): the sign code, the dual vertex and
-// l_dev, the ring table and the quad's orientation and split are flexi_core.h's functions, the ones k_flexi.inc calls, which is what
-// makes the vertices, faces and l_dev bitwise the dense ones.  What is written here is what differs: corner positions from the axis
-// tables, offsets and case codes through rank_of on the compact list, the orientation from the case code, the capacity checks.
-// The error plumbing, gid, the workgroup scan and the mask-word helpers are foho_side.h's; the workspace allocator is foho_carve.h's.
+//                   of a grid point gathers its at most 24 terms in a fixed order and stores once -- no float atomics.  The
+//                   ownership rule and the order of the walk are flexi_core.h's, shared with k_wf_bwd_gather; the terms are written here
+// Compiled with foho_step.hip's flags (-ffp-contract=off, correctly rounded division and sqrt): the index arithmetic, the sign code,
+// the dual vertex and l_dev, the ring table and the quad's orientation and split are flexi_core.h's, the ones k_flexi.inc calls, which
+// is what makes the vertices, faces and l_dev bitwise the dense ones.  What is written here is what differs: corner positions from the
+// axis tables, offsets and case codes through rank_of on the compact list, the orientation from the case code, the capacity checks.
+// The error plumbing, gid, usable_count, the workgroup scan and the mask-word helpers are foho_side.h's; the workspace allocator is
+// foho_carve.h's.
 #include "flexi_core.h"
 #include "foho_carve.h"
 #include "foho_side.h"
@@ -83,7 +85,7 @@ __global__ __launch_bounds__(TPB) void k_sf_mark(const float* __restrict__ s, in
     const int64_t p = gid(), n = (int64_t)res * res * res;
     bool m = false;
     if (p < n) {
-        const unsigned code = flexi_cube_code(s, res, (int)(p / ((int64_t)res * res)), (int)((p / res) % res), (int)(p % res));
+        const unsigned code = flexi_cube_code(s, res, FLEXI_I(p, res), FLEXI_J(p, res), FLEXI_K(p, res));
         m = code != 0u && code != 255u;
     }
     const uint64_t w = store_word(mask, p, n, m);
@@ -216,7 +218,7 @@ __global__ __launch_bounds__(TPB) void k_sf_classify(const float* __restrict__ s
     const int64_t cube = cid[c], C = (int64_t)res * res * res;
     unsigned code = 0, f = 0;
     if (cube >= 0 && cube < C) {
-        const int k = (int)(cube % res), j = (int)((cube / res) % res), i = (int)(cube / ((int64_t)res * res));
+        FLEXI_IJK(cube, res)
         code = flexi_cube_code(s, res, i, j, k);
         // the edge from the minimum corner along an axis ends at a grid point (i, j, k < res); it has four cubes around it when
         // its two transverse coordinates are interior; its ends are corners 0 and 1 / 2 / 4
@@ -244,13 +246,13 @@ __device__ __forceinline__ void sf_verts_role(int64_t c, int n, const float* __r
         return;
     }
     const int G = res + 1;
-    const int64_t t = cid[c];
-    const int k = (int)(t % res), j = (int)((t / res) % res), i = (int)(t / ((int64_t)res * res));
+    const int64_t cube = cid[c];
+    FLEXI_IJK(cube, res)
     float sc[8], xc[24];
 #pragma unroll
     for (int q = 0; q < 8; q++) {
         const int ci = i + (q & 1), cj = j + ((q >> 1) & 1), ck = k + (q >> 2);
-        sc[q] = s[((size_t)ci * G + cj) * G + ck];
+        sc[q] = s[flexi_point(ci, cj, ck, G)];
         xc[3 * q + 0] = axes[ci];
         xc[3 * q + 1] = axes[G + cj];
         xc[3 * q + 2] = axes[2 * G + ck];
@@ -273,7 +275,7 @@ __device__ __forceinline__ void sf_faces_role(int64_t t, int n, int res, const u
         return;
     }
     const int64_t cube = cid[c];
-    const int k = (int)(cube % res), j = (int)((cube / res) % res), i = (int)(cube / ((int64_t)res * res));
+    FLEXI_IJK(cube, res)
     int64_t q[4];
 #pragma unroll
     for (int r = 0; r < 4; r++) {
@@ -306,72 +308,52 @@ __global__ __launch_bounds__(TPB) void k_sf_emit(const float* __restrict__ axes,
         sf_faces_role((int64_t)(blockIdx.x - nvb) * TPB + threadIdx.x, n, res, mask, bpre, cid, cse, efl, off, faces, faces_cap, counts);
 }
 
-// dL/ds by gather: 8 threads per surface cube, one per corner.  Every grid point P that ends a crossing edge is a corner of a surface
-// cube; the thread whose cube has the lowest id among the marked cubes incident to P owns it.  The owner walks P's six grid edges
-// (axis 0 towards -, +, then axis 1, axis 2) and, on a crossing one, the in-grid cubes of the edge's ring in c_flexi_ring order: one
-// term of k_flexi_bwd per (edge, cube), at most 24, summed in that order into a register and stored once.  Positions come from the
-// axis tables, so of g . (x_a - x_b) only the edge's own axis is left.
+// dL/ds by gather (flexi_core.h: flexi_owns_point, flexi_walk_point): 8 threads per surface cube, one per corner; the owner of a grid
+// point P walks its six edges and, on a crossing one, the edge's ring: one term of k_flexi_bwd per (edge, cube), at most 24, summed in
+// that order into a register and stored once.  Positions come from the axis tables, so of g . (x_a - x_b) only the edge's own axis is
+// left.
 __global__ __launch_bounds__(TPB) void k_sf_bwd(const float* __restrict__ axes, const float* __restrict__ s, int res,
                                                 const uint64_t* __restrict__ mask, const int32_t* __restrict__ bpre,
                                                 const int32_t* __restrict__ total, int cube_cap, const int32_t* __restrict__ cid,
                                                 const uint8_t* __restrict__ cse, const int32_t* __restrict__ off,
                                                 const float* __restrict__ gverts, int n_verts, float* __restrict__ gs) {
-    const int n = *total;
-    if (n <= 0 || n > cube_cap) return;
+    const int n = usable_count(*total, cube_cap);
     const int64_t t = gid();
     if (t >= 8 * (int64_t)n) return;
-    const int q = (int)(t & 7);
     const int64_t cube = cid[t >> 3], C = (int64_t)res * res * res;
     if (cube < 0 || cube >= C) return;
     const int G = res + 1;
-    // the grid point
-    const int pt[3] = {(int)(cube / ((int64_t)res * res)) + (q & 1), (int)((cube / res) % res) + ((q >> 1) & 1), (int)(cube % res) + (q >> 2)};
-    // owner: no marked cube of a lower id among the in-grid cubes incident to P
-#pragma unroll
-    for (int o = 0; o < 8; o++) {
-        const int ci = pt[0] - (o & 1), cj = pt[1] - ((o >> 1) & 1), ck = pt[2] - (o >> 2);
-        if (ci < 0 || cj < 0 || ck < 0 || ci >= res || cj >= res || ck >= res) continue;
-        const int64_t other = ((int64_t)ci * res + cj) * res + ck;
-        if (other < cube && ((mask[other >> 6] >> (other & 63)) & 1ull)) return;
-    }
-    const float sp = s[((size_t)pt[0] * G + pt[1]) * G + pt[2]];
-    float acc = 0.f;
+    int pt[3];
+    if (!flexi_owns_point(cube, (int)(t & 7), res, pt, [&](int64_t c) { return (mask[c >> 6] >> (c & 63)) & 1ull; })) return;
+    const size_t gp = flexi_point(pt[0], pt[1], pt[2], G);
+    const float sp = s[gp];
+    float acc = 0.f, w = 0.f, dx = 0.f;  // w dx: the crossing edge's d crossing / d s_P along its axis
     bool any = false;
-#pragma unroll
-    for (int axis = 0; axis < 3; axis++) {
-#pragma unroll
-        for (int side = 0; side < 2; side++) {
-            // the edge from M (its lower end, corner a) along +axis; P is a when side == 1
-            const int m = pt[axis] - 1 + side;
-            if (m < 0 || m >= res) continue;
-            const int mi = axis == 0 ? m : pt[0], mj = axis == 1 ? m : pt[1], mk = axis == 2 ? m : pt[2];
-            const int oi = mi + (axis == 0), oj = mj + (axis == 1), ok = mk + (axis == 2);
-            const float so = side ? s[((size_t)oi * G + oj) * G + ok] : s[((size_t)mi * G + mj) * G + mk];
-            if ((sp < 0.0f) == (so < 0.0f)) continue;
+    flexi_walk_point(
+        pt, res,
+        [&](int axis, int side, int mi, int mj, int mk) {
+            const float so = s[flexi_point(mi + (side && axis == 0), mj + (side && axis == 1), mk + (side && axis == 2), G)];
+            if ((sp < 0.0f) == (so < 0.0f)) return false;
             any = true;
             const float sa = side ? sp : so, sb = side ? so : sp;
             const float D = sb - sa;
             // (s / D) / D as k_flexi_bwd: |s / D| <= 1 on a crossing edge
-            const float w = (side ? sb / D : -sa / D) / D;
-            const float dx = axes[axis * G + m] - axes[axis * G + m + 1];
-            for (int r = 0; r < 4; r++) {
-                const int ci = mi + c_flexi_ring[axis][r][0], cj = mj + c_flexi_ring[axis][r][1], ck = mk + c_flexi_ring[axis][r][2];
-                if (ci < 0 || cj < 0 || ck < 0 || ci >= res || cj >= res || ck >= res) continue;  // boundary edge: fewer than four cubes
-                const int rk = rank_of(mask, bpre, ((int64_t)ci * res + cj) * res + ck);
-                if ((unsigned)rk >= (unsigned)n) continue;  // (a mark buffer of another field)
-                const unsigned code = cse[rk];
-                const int p = c_flexi_edge_patch[code][c_flexi_ring[axis][r][3]];
-                if (p < 0) continue;  // (a workspace of another field)
-                const int v = off[rk] + p;
-                if ((unsigned)v >= (unsigned)n_verts) continue;
-                float cnt = 0.f;
-#pragma unroll
-                for (int e = 0; e < 12; e++) cnt += (c_flexi_edge_patch[code][e] == p) ? 1.0f : 0.0f;
-                acc += (gverts[3 * (size_t)v + axis] / cnt) * dx * w;
-            }
-        }
-    }
-    if (any) gs[((size_t)pt[0] * G + pt[1]) * G + pt[2]] = acc;
+            w = (side ? sb / D : -sa / D) / D;
+            const int m = axis == 0 ? mi : (axis == 1 ? mj : mk);
+            dx = axes[axis * G + m] - axes[axis * G + m + 1];
+            return true;
+        },
+        [&](int axis, int, int64_t cc, int e) {
+            const int rk = rank_of(mask, bpre, cc);
+            if ((unsigned)rk >= (unsigned)n) return;  // (a mark buffer of another field)
+            const unsigned code = cse[rk];
+            const int p = c_flexi_edge_patch[code][e];
+            if (p < 0) return;  // (a workspace of another field)
+            const int v = off[rk] + p;
+            if ((unsigned)v >= (unsigned)n_verts) return;
+            acc += (gverts[3 * (size_t)v + axis] / flexi_patch_edges(code, p)) * dx * w;
+        });
+    if (any) gs[gp] = acc;
 }
 
 bool res_ok(int32_t r) { return r >= 1 && r <= FOHO_SFLEXI_MAX_RES; }

@@ -2,7 +2,7 @@
 // anonymous namespace, so a library that includes it exports nothing new.
 //
 // Host: the error string behind foho_<name>_last_error, fail / launched, blocks_for, and FOHO_SIDE_ENTRY_POINTS for the version and
-// last-error entry points.  Device: gid, the workgroup scan, and the mask-word helpers (64 points per word, a wave owns a word).
+// last-error entry points.  Device: gid, usable_count, the workgroup scan, and the mask-word helpers (64 points per word, a wave owns a word).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -35,6 +35,10 @@ unsigned blocks_for(size_t n, int per = TPB) { return (unsigned)(n ? (n + per - 
     extern "C" API const char* foho_##name##_last_error(void) { return g_err.c_str(); }
 
 __device__ __forceinline__ int64_t gid() { return (int64_t)blockIdx.x * TPB + threadIdx.x; }
+
+// a count an earlier kernel left on the device, as far as the buffers carved for `cap` items can be trusted with it: n when
+// 0 <= n <= cap, else 0 (an overflow, or a workspace of another field)
+__device__ __forceinline__ int usable_count(int n, int cap) { return (n < 0 || n > cap) ? 0 : n; }
 
 // exclusive scan over the N threads of a workgroup in LDS (Hillis-Steele; s: N items): this thread's exclusive prefix.  The inclusive
 // sums stay in s behind the last barrier (the workgroup's total is s[N - 1]).

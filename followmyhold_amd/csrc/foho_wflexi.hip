@@ -7,15 +7,20 @@
 //   k_wf_blocks     one workgroup: exclusive scan of the block counts, the totals
 //   k_wf_offsets    one thread per cube: the scan inside the block -> rank of a surface cube (dense, int32) and, by rank, its id, its
 //                   vertex offset and its three quad indices; the counts
-//   k_wf_verts      per surface cube: dual vertices and l_dev (wflexi_core.h)
-//   k_wf_faces      per (surface cube, axis): the quad of the owned edge, oriented by flexi_quad; split by gamma, or the centre and
-//                   four triangles.  A launch of its own because the centre reads the four dual vertices
+//   k_wf_verts      per surface cube: dual vertices and l_dev (flexi_dual_vertex with the weights)
+//   k_wf_faces      per (surface cube, axis): the quad of the owned edge, ids and gammas oriented by flexi_orient; flexi_split along
+//                   the diagonal gamma chooses, or the centre and four triangles.  A launch of its own because the centre reads the
+//                   four dual vertices
 //   k_wf_bwd_cube   per surface cube: dL/dalpha and dL/dbeta rows, dL/dgamma and the centres' gradient to its dual vertices by a walk
-//                   over the quads of its twelve edges, and one float4 record (dL/ds, dL/dx) per (edge, end)
-//   k_wf_bwd_gather 8 threads per surface cube: the owner of a grid point sums its at most 24 records and stores once
+//                   over the quads of its twelve edges, and one float4 record (dL/ds, dL/dx) per (edge, end); the forward's
+//                   quantities come from one call of flexi_dual_vertex per patch
+//   k_wf_bwd_gather 8 threads per surface cube: the owner of a grid point sums its at most 24 records and stores once (flexi_core.h's
+//                   ownership rule and walk, k_sf_bwd's)
 // Everything behind k_wf_offsets works on the list of surface cubes.  STRICT flags (-ffp-contract=off, correctly rounded division and
-// sqrt), as foho_sflexi.hip: with unit weights the vertices, l_dev and faces are bitwise foho_flexi_fwd's.
-#include "wflexi_core.h"
+// sqrt), as foho_sflexi.hip, and the per-cube arithmetic is flexi_core.h's, the one the dense and sparse extractors call without
+// weights: with unit weights the vertices, l_dev and faces are bitwise foho_flexi_fwd's.  What is written here is the list of surface
+// cubes, the weight rows, the centres of training mode and the backward's own terms.
+#include "flexi_core.h"
 #include "foho_carve.h"
 #include "foho_side.h"
 #include "foho_wflexi.h"
@@ -87,7 +92,7 @@ __global__ __launch_bounds__(TPB) void k_wf_classify(const float* __restrict__ s
     const int64_t p = gid(), C = (int64_t)res * res * res;
     unsigned v = 0;
     if (p < C) {
-        const int k = (int)(p % res), j = (int)((p / res) % res), i = (int)(p / ((int64_t)res * res));
+        FLEXI_IJK(p, res)
         const unsigned code = flexi_cube_code(s, res, i, j, k);
         // the edge from the minimum corner along an axis has four cubes around it when its two transverse coordinates are interior; its
         // ends are corners 0 and 1 / 2 / 4
@@ -150,13 +155,16 @@ __global__ __launch_bounds__(TPB) void k_wf_offsets(const uint16_t* __restrict__
     }
 }
 
+// corner values, corner positions and the cube's rows of alpha and beta (1 where the weight is not given).  The corner part is
+// k_flexi.inc's flexi_corners with the alpha row between its loads: split in two calls, k_wf_verts takes four registers more and
+// loses a wave of occupancy
 __device__ __forceinline__ void load_cube(const float* __restrict__ x, const float* __restrict__ s, const float* __restrict__ alpha,
                                           const float* __restrict__ beta, int res, int64_t cube, float* sc, float* xc, float* al, float* be) {
     const int G = res + 1;
-    const int k = (int)(cube % res), j = (int)((cube / res) % res), i = (int)(cube / ((int64_t)res * res));
+    FLEXI_IJK(cube, res)
 #pragma unroll
     for (int c = 0; c < 8; c++) {
-        const size_t gi = ((size_t)(i + (c & 1)) * G + (j + ((c >> 1) & 1))) * G + (k + (c >> 2));
+        const size_t gi = flexi_corner(i, j, k, c, G);
         sc[c] = s[gi];
         for (int q = 0; q < 3; q++) xc[3 * c + q] = x[3 * gi + q];
         al[c] = alpha ? alpha[8 * (size_t)cube + c] : 1.0f;
@@ -165,19 +173,13 @@ __device__ __forceinline__ void load_cube(const float* __restrict__ x, const flo
     for (int e = 0; e < 12; e++) be[e] = beta ? beta[12 * (size_t)cube + e] : 1.0f;
 }
 
-// the list is usable: the forward's totals fit the capacities the workspace was carved for
-__device__ __forceinline__ int list_len(const int32_t* total, int cap) {
-    const int n = total[0];
-    return (n < 0 || n > cap) ? 0 : n;
-}
-
 __global__ __launch_bounds__(TPB) void k_wf_verts(const float* __restrict__ x, const float* __restrict__ s, const float* __restrict__ alpha,
                                                   const float* __restrict__ beta, int res, const uint16_t* __restrict__ info,
                                                   const int32_t* __restrict__ total, int cap, const int32_t* __restrict__ cid,
                                                   const int32_t* __restrict__ voff, float* __restrict__ verts, float* __restrict__ ldev,
                                                   int32_t* counts) {
     const int64_t t = gid();
-    if (t >= list_len(total, cap)) return;
+    if (t >= usable_count(total[0], cap)) return;
     const int64_t cube = cid[t];
     if (cube < 0 || cube >= (int64_t)res * res * res) return;  // (a workspace of another resolution)
     const unsigned code = info[cube] & 255u;
@@ -188,8 +190,7 @@ __global__ __launch_bounds__(TPB) void k_wf_verts(const float* __restrict__ x, c
     }
     float sc[8], xc[24], al[8], be[12];
     load_cube(x, s, alpha, beta, res, cube, sc, xc, al, be);
-    for (int p = 0; p < np; p++)
-        wflexi_dual_vertex(code, p, sc, xc, al, be, verts + 3 * (size_t)(base + p), nullptr, ldev ? ldev + (base + p) : nullptr);
+    for (int p = 0; p < np; p++) flexi_dual_vertex(code, p, sc, xc, al, be, verts + 3 * (size_t)(base + p), ldev ? ldev + (base + p) : nullptr);
 }
 
 // the ring of the axis-`axis` edge that starts at grid point (i,j,k), all four cubes in the grid: their ids and ranks
@@ -210,7 +211,7 @@ __global__ __launch_bounds__(TPB) void k_wf_faces(const float* __restrict__ gamm
                                                   const int32_t* __restrict__ qoff, float* __restrict__ verts, int64_t* __restrict__ faces,
                                                   int faces_cap, int32_t* counts) {
     const int64_t t = gid();
-    const int n = list_len(total, cap);
+    const int n = usable_count(total[0], cap);
     if (t >= 3 * (int64_t)n) return;
     const int axis = (int)(t % 3);
     const int64_t c = t / 3;
@@ -227,8 +228,8 @@ __global__ __launch_bounds__(TPB) void k_wf_faces(const float* __restrict__ gamm
     }
     const int64_t cube = cid[c];
     if (cube < 0 || cube >= (int64_t)res * res * res) return;
-    const int k = (int)(cube % res), j = (int)((cube / res) % res), i = (int)(cube / ((int64_t)res * res));
-    int64_t cc[4], q[4], o[6];
+    FLEXI_IJK(cube, res)
+    int64_t cc[4], q[4];
     int rk[4];
     if (!ring_of(axis, i, j, k, res, rank, n, cc, rk)) return;
     float g[4];
@@ -238,15 +239,11 @@ __global__ __launch_bounds__(TPB) void k_wf_faces(const float* __restrict__ gamm
         g[r] = gamma ? gamma[cc[r]] : 1.0f;
     }
     const bool near_inside = info[cube] & 1u;  // the edge's near end is corner 0 of this cube
-    flexi_quad(q, near_inside, o);
-    if (!near_inside) {
-        const float t0 = g[0], t1 = g[1];
-        g[0] = g[3], g[1] = g[2], g[2] = t1, g[3] = t0;
-    }
+    flexi_orient(q, near_inside);
+    flexi_orient(g, near_inside);
     int64_t* out = faces + 3 * (size_t)per * qd;
     if (!training) {
-        wflexi_split(q, g, o);
-        for (int m = 0; m < 6; m++) out[m] = o[m];
+        flexi_split(q, g[1] * g[3] > g[0] * g[2], out);  // the second diagonal only where its product is strictly larger
         return;
     }
     const float g02 = g[0] * g[2], g13 = g[1] * g[3], den = (g02 + g13) + 1e-8f;
@@ -275,16 +272,16 @@ __global__ __launch_bounds__(TPB) void k_wf_bwd_cube(BwdArgs A, const uint16_t* 
                                                      const int32_t* __restrict__ total, const int32_t* __restrict__ cid,
                                                      const int32_t* __restrict__ voff, const int32_t* __restrict__ qoff) {
     FLEXI_EDGE_TABLES
-    WFLEXI_RING_TABLE
+    FLEXI_RING_TABLE
     const int64_t t = gid();
-    const int n = list_len(total, A.cap), res = A.res;
+    const int n = usable_count(total[0], A.cap), res = A.res;
     if (t >= n || total[1] != A.n_verts) return;
     const int64_t cube = cid[t];
     if (cube < 0 || cube >= (int64_t)res * res * res) return;
     const unsigned code = info[cube] & 255u;
     const int np = c_flexi_npatch[code], base = voff[t];
     if (base < 0 || base + np > A.n_verts) return;
-    const int k = (int)(cube % res), j = (int)((cube / res) % res), i = (int)(cube / ((int64_t)res * res));
+    FLEXI_IJK(cube, res)
     float sc[8], xc[24], al[8], be[12];
     load_cube(A.x, A.s, A.alpha, A.beta, res, cube, sc, xc, al, be);
     float ga[8], gb[12], ggam = 0.f;
@@ -335,25 +332,12 @@ __global__ __launch_bounds__(TPB) void k_wf_bwd_cube(BwdArgs A, const uint16_t* 
                 ggam += dotg * g_opp;
             }
         }
-        // forward again: v, the weight sum, the distances to the unweighted crossings
-        float v[3], B, cnt = 0.f, dd[12], dsum = 0.f;
-        wflexi_dual_vertex(code, p, sc, xc, al, be, v, &B, nullptr);
-#pragma unroll
-        for (int e = 0; e < 12; e++) {
-            dd[e] = 0.f;
-            if (c_flexi_edge_patch[code][e] != p) continue;
-            const int a = fx_ea[e], b = fx_eb[e];
-            const float D = sc[b] - sc[a];
-            float d2 = 0.f;
-            for (int q = 0; q < 3; q++) {
-                const float u = (xc[3 * a + q] * sc[b] - xc[3 * b + q] * sc[a]) / D - v[q];
-                d2 += u * u;
-            }
-            dd[e] = sqrtf(d2);
-            dsum += dd[e];
-            cnt += 1.0f;
-        }
-        const float mean = dsum / cnt;
+        // the forward's v, weight sum, edge count, distances to the unweighted crossings and their mean
+        float v[3];
+        FlexiDual fd;
+        flexi_dual_vertex(code, p, sc, xc, al, be, v, nullptr, &fd);
+        const float B = fd.B, cnt = fd.cnt, mean = fd.mean;
+        const float* dd = fd.dd;
         float ssum = 0.f;
 #pragma unroll
         for (int e = 0; e < 12; e++)
@@ -410,56 +394,36 @@ __global__ __launch_bounds__(TPB) void k_wf_bwd_cube(BwdArgs A, const uint16_t* 
     if (A.ggamma && A.training) A.ggamma[cube] = ggam;
 }
 
-// 8 threads per surface cube, one per corner.  Every grid point P that ends a crossing edge is a corner of a surface cube; the thread
-// whose cube has the lowest id among the surface cubes that touch P owns it (k_sf_bwd's rule).  The owner walks P's six grid edges
-// (axis 0 towards -, +, then axis 1, axis 2) and the in-grid cubes of each edge's ring in c_flexi_ring order, and adds the record of
-// every (cube, edge) in which the edge crosses.
+// the gather of flexi_core.h (flexi_owns_point, flexi_walk_point; k_sf_bwd's): 8 threads per surface cube, one per corner; the owner of
+// a grid point adds the record of every (ring cube, edge) in which one of its six edges crosses, and stores once.
 __global__ __launch_bounds__(TPB) void k_wf_bwd_gather(const float4* __restrict__ rec, int res, int cap, const uint16_t* __restrict__ info,
                                                        const int32_t* __restrict__ rank, const int32_t* __restrict__ total,
                                                        const int32_t* __restrict__ cid, float* __restrict__ gs, float* __restrict__ gx) {
-    const int n = list_len(total, cap);
+    const int n = usable_count(total[0], cap);
     const int64_t t = gid();
     if (t >= 8 * (int64_t)n) return;
-    const int q = (int)(t & 7);
     const int64_t cube = cid[t >> 3];
     if (cube < 0 || cube >= (int64_t)res * res * res) return;
-    const int G = res + 1;
-    const int pt[3] = {(int)(cube / ((int64_t)res * res)) + (q & 1), (int)((cube / res) % res) + ((q >> 1) & 1), (int)(cube % res) + (q >> 2)};
-#pragma unroll
-    for (int o = 0; o < 8; o++) {
-        const int ci = pt[0] - (o & 1), cj = pt[1] - ((o >> 1) & 1), ck = pt[2] - (o >> 2);
-        if (ci < 0 || cj < 0 || ck < 0 || ci >= res || cj >= res || ck >= res) continue;
-        const int64_t other = ((int64_t)ci * res + cj) * res + ck;
-        const unsigned oc = info[other] & 255u;
-        if (other < cube && oc != 0u && oc != 255u) return;
-    }
+    int pt[3];
+    const auto is_surface = [&](int64_t c) {
+        const unsigned oc = info[c] & 255u;
+        return oc != 0u && oc != 255u;
+    };
+    if (!flexi_owns_point(cube, (int)(t & 7), res, pt, is_surface)) return;
     float as = 0.f, ax[3] = {0.f, 0.f, 0.f};
     bool any = false;
-#pragma unroll
-    for (int axis = 0; axis < 3; axis++) {
-#pragma unroll
-        for (int side = 0; side < 2; side++) {
-            // the edge from M (its lower end, corner a) along +axis; P is a when side == 1
-            const int m = pt[axis] - 1 + side;
-            if (m < 0 || m >= res) continue;
-            const int mi = axis == 0 ? m : pt[0], mj = axis == 1 ? m : pt[1], mk = axis == 2 ? m : pt[2];
-            for (int r = 0; r < 4; r++) {
-                const int ci = mi + c_flexi_ring[axis][r][0], cj = mj + c_flexi_ring[axis][r][1], ck = mk + c_flexi_ring[axis][r][2];
-                if (ci < 0 || cj < 0 || ck < 0 || ci >= res || cj >= res || ck >= res) continue;  // boundary edge: fewer than four cubes
-                const int64_t cc = ((int64_t)ci * res + cj) * res + ck;
-                const unsigned code = info[cc] & 255u;
-                const int e = c_flexi_ring[axis][r][3];
-                if (c_flexi_edge_patch[code][e] < 0) continue;  // the edge does not cross (or the cube is no surface cube)
-                const int rk = rank[cc];
-                if ((unsigned)rk >= (unsigned)n) continue;
-                const float4 v = rec[((size_t)rk * 12 + e) * 2 + (side ? 0 : 1)];
-                as += v.x, ax[0] += v.y, ax[1] += v.z, ax[2] += v.w;
-                any = true;
-            }
-        }
-    }
+    flexi_walk_point(
+        pt, res, [](int, int, int, int, int) { return true; },
+        [&](int, int side, int64_t cc, int e) {
+            if (c_flexi_edge_patch[info[cc] & 255u][e] < 0) return;  // the edge does not cross (or the cube is no surface cube)
+            const int rk = rank[cc];
+            if ((unsigned)rk >= (unsigned)n) return;
+            const float4 v = rec[((size_t)rk * 12 + e) * 2 + (side ? 0 : 1)];
+            as += v.x, ax[0] += v.y, ax[1] += v.z, ax[2] += v.w;
+            any = true;
+        });
     if (!any) return;
-    const size_t gi = ((size_t)pt[0] * G + pt[1]) * G + pt[2];
+    const size_t gi = flexi_point(pt[0], pt[1], pt[2], res + 1);
     if (gs) gs[gi] = as;
     if (gx)
         for (int m = 0; m < 3; m++) gx[3 * gi + m] = ax[m];
@@ -524,7 +488,7 @@ FOHO_WFLEXI_API int foho_wflexi_bwd(const float* x, const float* s, const float*
     A.galpha = grad_alpha, A.gbeta = grad_beta, A.ggamma = training ? grad_gamma : nullptr;
     A.rec = want_rec ? (float4*)scratch : nullptr;
     A.res = res, A.training = training, A.n_verts = n_verts, A.n_all = n_all, A.cap = n_cubes;
-    // the list is n_cubes long: a workspace of another field (another count) is refused by list_len
+    // the list is n_cubes long: a workspace of another field (another count) is refused by usable_count
     hipLaunchKernelGGL(k_wf_bwd_cube, dim3(blocks_for((size_t)n_cubes)), dim3(TPB), 0, st, A, w.info, w.rank, w.tot, w.cid, w.voff, w.qoff);
     if (want_rec)
         hipLaunchKernelGGL(k_wf_bwd_gather, dim3(blocks_for(8 * (size_t)n_cubes)), dim3(TPB), 0, st, (const float4*)scratch, res, n_cubes,

@@ -14,8 +14,9 @@
 //
 // Grid point (i,j,k) -> (i*G + j)*G + k (generate_dense_grid_points, PL:341-360); cube corners in x-fastest order; cube edges
 // 0-3 along x, 4-7 along y, 8-11 along z (followmyhold_amd/flexi_tables.py).
-// The per-cube arithmetic (sign code, dual vertex and l_dev, ring table, quad orientation and split) is flexi_core.h's, shared with the
-// sparse extractor (foho_sflexi.hip).
+// The per-cube arithmetic (index helpers, sign code, dual vertex and l_dev, patch edge count, ring table, quad orientation and split) is
+// flexi_core.h's, shared with the sparse extractor (foho_sflexi.hip) and the weighted one (foho_wflexi.hip).  The five scan kernels
+// are three device functions (scan_load8, scan_block_sum, scan_store8) around their own choice of array and prefix.
 #include "flexi_core.h"
 
 constexpr int FX_ITEMS = 2048;  // items per workgroup of the scan (256 threads x 8)
@@ -52,7 +53,7 @@ __global__ __launch_bounds__(256) void k_flexi_classify(const float* s, int res,
     const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
     const size_t C = (size_t)res * res * res, G3 = (size_t)G * G * G;
     if (t < C) {
-        const int k = (int)(t % res), j = (int)((t / res) % res), i = (int)(t / ((size_t)res * res));
+        FLEXI_IJK(t, res)
         const unsigned code = flexi_cube_code(s, res, i, j, k);
         cse[t] = (uint8_t)code;
         npatch[t] = c_flexi_npatch[code];
@@ -60,7 +61,7 @@ __global__ __launch_bounds__(256) void k_flexi_classify(const float* s, int res,
     if (t < 3 * G3) {
         const int axis = (int)(t / G3);
         const size_t r = t % G3;
-        const int k = (int)(r % G), j = (int)((r / G) % G), i = (int)(r / ((size_t)G * G));
+        FLEXI_IJK(r, G)
         const int di = axis == 0, dj = axis == 1, dk = axis == 2;
         int flag = 0;
         // the edge exists when its far end is a grid point; it has four cubes when the two transverse coordinates are interior
@@ -68,6 +69,7 @@ __global__ __launch_bounds__(256) void k_flexi_classify(const float* s, int res,
         const bool t1 = di ? (j >= 1 && j <= res - 1) : (i >= 1 && i <= res - 1);
         const bool t2 = dk ? (j >= 1 && j <= res - 1) : (k >= 1 && k <= res - 1);
         if (along && t1 && t2) {
+            // (flexi_point written out: through the call the compiler orders this kernel's instructions differently)
             const float sa = s[r], sb = s[((size_t)(i + di) * G + (j + dj)) * G + (k + dk)];
             flag = ((sa < 0.0f) != (sb < 0.0f)) ? 1 : 0;
         }
@@ -75,17 +77,48 @@ __global__ __launch_bounds__(256) void k_flexi_classify(const float* s, int res,
     }
 }
 
-// ---- exclusive scan of an int32 array (three launches; deterministic)
-__global__ __launch_bounds__(256) void k_scan_sums(const int32_t* in, size_t n, int32_t* bsum) {
-    __shared__ int s_w[4];
-    const size_t base = (size_t)blockIdx.x * FX_ITEMS + (size_t)threadIdx.x * 8;
+// ---- exclusive scan of an int32 array (three launches; deterministic).  A workgroup takes FX_ITEMS items, 8 in a row per thread.
+// The three pieces of its kernels; s_w = 4 ints of LDS:
+// my 8 items of `in` (0 past n) -> v; their sum
+__device__ __forceinline__ int scan_load8(const int32_t* in, size_t base, size_t n, int* v) {
+    int sum = 0;
+#pragma unroll
+    for (int q = 0; q < 8; q++) {
+        v[q] = (base + q < n) ? in[base + q] : 0;
+        sum += v[q];
+    }
+    return sum;
+}
+// the sum of the workgroup's items (one barrier)
+__device__ __forceinline__ int scan_block_sum(const int32_t* in, size_t base, size_t n, int* s_w) {
     int v = 0;
 #pragma unroll
     for (int q = 0; q < 8; q++) v += (base + q < n) ? in[base + q] : 0;
     const unsigned w = wave_sum((unsigned)v);
     if (lane_id() == 0) s_w[wave_id()] = (int)w;
     __syncthreads();
-    if (threadIdx.x == 0) bsum[blockIdx.x] = (s_w[0] + s_w[1]) + (s_w[2] + s_w[3]);
+    return (s_w[0] + s_w[1]) + (s_w[2] + s_w[3]);
+}
+// the exclusive prefixes of my 8 items -> out, given the total in front of the workgroup (one barrier); the running total behind my
+// last item
+__device__ __forceinline__ int scan_store8(const int* v, int sum, int prefix, size_t base, size_t n, int32_t* out, int* s_w) {
+    const unsigned incl = wave_incl_scan((unsigned)sum);
+    if (lane_id() == 63) s_w[wave_id()] = (int)incl;
+    __syncthreads();
+    int off = prefix + (int)incl - sum;
+    for (int w = 0; w < wave_id(); w++) off += s_w[w];
+#pragma unroll
+    for (int q = 0; q < 8; q++) {
+        if (base + q < n) out[base + q] = off;
+        off += v[q];
+    }
+    return off;
+}
+
+__global__ __launch_bounds__(256) void k_scan_sums(const int32_t* in, size_t n, int32_t* bsum) {
+    __shared__ int s_w[4];
+    const int sum = scan_block_sum(in, (size_t)blockIdx.x * FX_ITEMS + (size_t)threadIdx.x * 8, n, s_w);
+    if (threadIdx.x == 0) bsum[blockIdx.x] = sum;
 }
 __global__ __launch_bounds__(256) void k_scan_bsums(int32_t* bsum, int nb, int32_t* total) {
     // one workgroup: exclusive scan of the block sums in place, total appended at bsum[nb] and stored to *total
@@ -114,22 +147,9 @@ __global__ __launch_bounds__(256) void k_scan_bsums(int32_t* bsum, int nb, int32
 __global__ __launch_bounds__(256) void k_scan_apply(const int32_t* in, size_t n, const int32_t* bsum, int32_t* out) {
     __shared__ int s_w[4];
     const size_t base = (size_t)blockIdx.x * FX_ITEMS + (size_t)threadIdx.x * 8;
-    int v[8], sum = 0;
-#pragma unroll
-    for (int q = 0; q < 8; q++) {
-        v[q] = (base + q < n) ? in[base + q] : 0;
-        sum += v[q];
-    }
-    const unsigned incl = wave_incl_scan((unsigned)sum);
-    if (lane_id() == 63) s_w[wave_id()] = (int)incl;
-    __syncthreads();
-    int off = bsum[blockIdx.x] + (int)incl - sum;
-    for (int w = 0; w < wave_id(); w++) off += s_w[w];
-#pragma unroll
-    for (int q = 0; q < 8; q++) {
-        if (base + q < n) out[base + q] = off;
-        off += v[q];
-    }
+    int v[8];
+    const int sum = scan_load8(in, base, n, v);
+    scan_store8(v, sum, bsum[blockIdx.x], base, n, out, s_w);  // bsum: scanned by k_scan_bsums
 }
 
 // the two scans of the extraction (dual vertices per cube, quads per grid edge) ride in the same three launches
@@ -144,16 +164,8 @@ __global__ __launch_bounds__(256) void k_scan2_sums(Scan2 a) {
     __shared__ int s_w[4];
     const int which = ((int)blockIdx.x < a.nb[0]) ? 0 : 1;
     const int blk = which ? blockIdx.x - a.nb[0] : blockIdx.x;
-    const int32_t* in = which ? a.in[1] : a.in[0];
-    const size_t n = which ? a.n[1] : a.n[0];
-    const size_t base = (size_t)blk * FX_ITEMS + (size_t)threadIdx.x * 8;
-    int v = 0;
-#pragma unroll
-    for (int q = 0; q < 8; q++) v += (base + q < n) ? in[base + q] : 0;
-    const unsigned w = wave_sum((unsigned)v);
-    if (lane_id() == 0) s_w[wave_id()] = (int)w;
-    __syncthreads();
-    if (threadIdx.x == 0) (which ? a.bsum[1] : a.bsum[0])[blk] = (s_w[0] + s_w[1]) + (s_w[2] + s_w[3]);
+    const int sum = scan_block_sum(which ? a.in[1] : a.in[0], (size_t)blk * FX_ITEMS + (size_t)threadIdx.x * 8, which ? a.n[1] : a.n[0], s_w);
+    if (threadIdx.x == 0) (which ? a.bsum[1] : a.bsum[0])[blk] = sum;
 }
 // exclusive prefix of the block sums in front of workgroup `blk`, computed by the workgroup itself (at most a few hundred
 // values: cheaper than a launch for a serial scan of them).  Whole workgroup; s_w = 4 ints of LDS.  Ends with a barrier.
@@ -178,23 +190,10 @@ __global__ __launch_bounds__(256) void k_scan2_apply(Scan2 a, int32_t* counts) {
     int32_t* out = which ? a.out[1] : a.out[0];
     const size_t n = which ? a.n[1] : a.n[0];
     const size_t base = (size_t)blk * FX_ITEMS + (size_t)threadIdx.x * 8;
-    int v[8], sum = 0;
-#pragma unroll
-    for (int q = 0; q < 8; q++) {
-        v[q] = (base + q < n) ? in[base + q] : 0;
-        sum += v[q];
-    }
+    int v[8];
+    const int sum = scan_load8(in, base, n, v);
     const int prefix = block_prefix(bsum, blk, s_w);
-    const unsigned incl = wave_incl_scan((unsigned)sum);
-    if (lane_id() == 63) s_w[wave_id()] = (int)incl;
-    __syncthreads();
-    int off = prefix + (int)incl - sum;
-    for (int w = 0; w < wave_id(); w++) off += s_w[w];
-#pragma unroll
-    for (int q = 0; q < 8; q++) {
-        if (base + q < n) out[base + q] = off;
-        off += v[q];
-    }
+    const int off = scan_store8(v, sum, prefix, base, n, out, s_w);
     if (counts && blk == (which ? a.nb[1] : a.nb[0]) - 1 && threadIdx.x == 255) {  // off = grand total after the last item
         if (which == 0) {
             counts[0] = off;
@@ -208,31 +207,18 @@ __global__ __launch_bounds__(256) void k_scan2_apply(Scan2 a, int32_t* counts) {
 __global__ __launch_bounds__(256) void k_scan_apply_p(const int32_t* in, size_t n, const int32_t* bsum, int32_t* out) {
     __shared__ int s_w[4];
     const size_t base = (size_t)blockIdx.x * FX_ITEMS + (size_t)threadIdx.x * 8;
-    int v[8], sum = 0;
-#pragma unroll
-    for (int q = 0; q < 8; q++) {
-        v[q] = (base + q < n) ? in[base + q] : 0;
-        sum += v[q];
-    }
+    int v[8];
+    const int sum = scan_load8(in, base, n, v);
     const int prefix = block_prefix(bsum, (int)blockIdx.x, s_w);
-    const unsigned incl = wave_incl_scan((unsigned)sum);
-    if (lane_id() == 63) s_w[wave_id()] = (int)incl;
-    __syncthreads();
-    int off = prefix + (int)incl - sum;
-    for (int w = 0; w < wave_id(); w++) off += s_w[w];
-#pragma unroll
-    for (int q = 0; q < 8; q++) {
-        if (base + q < n) out[base + q] = off;
-        off += v[q];
-    }
+    scan_store8(v, sum, prefix, base, n, out, s_w);
 }
 
 __device__ __forceinline__ void flexi_corners(const float* x, const float* s, int res, size_t t, float* sc, float* xc) {
     const int G = res + 1;
-    const int k = (int)(t % res), j = (int)((t / res) % res), i = (int)(t / ((size_t)res * res));
+    FLEXI_IJK(t, res)
 #pragma unroll
     for (int c = 0; c < 8; c++) {
-        const size_t gi = ((size_t)(i + (c & 1)) * G + (j + ((c >> 1) & 1))) * G + (k + (c >> 2));
+        const size_t gi = flexi_corner(i, j, k, c, G);
         sc[c] = s[gi];
         for (int q = 0; q < 3; q++) xc[3 * c + q] = x[3 * gi + q];
     }
@@ -267,7 +253,7 @@ __device__ __forceinline__ void flexi_faces_role(size_t t, const float* s, int r
     }
     const int axis = (int)(t / G3);
     const size_t r = t % G3;
-    const int k = (int)(r % G), j = (int)((r / G) % G), i = (int)(r / ((size_t)G * G));
+    FLEXI_IJK(r, G)
     int64_t q[4];
 #pragma unroll
     for (int c = 0; c < 4; c++) {
@@ -333,23 +319,20 @@ __global__ __launch_bounds__(256) void k_flexi_bwd(const float* x, const float* 
     const int base = v_off[t];
     if (base + np > n_verts) return;
     const int G = res + 1;
-    const int k = (int)(t % res), j = (int)((t / res) % res), i = (int)(t / ((size_t)res * res));
+    FLEXI_IJK(t, res)
     FLEXI_EDGE_TABLES
     const unsigned code = cse[t];
     float sc[8], xc[24];
     flexi_corners(x, s, res, t, sc, xc);
     for (int p = 0; p < np; p++) {
-        float cnt = 0.f;
-#pragma unroll
-        for (int e = 0; e < 12; e++) cnt += (c_flexi_edge_patch[code][e] == p) ? 1.0f : 0.0f;
+        const float cnt = flexi_patch_edges(code, p);
         float g[3];
         for (int q = 0; q < 3; q++) g[q] = gverts[3 * (size_t)(base + p) + q] / cnt;
 #pragma unroll
         for (int e = 0; e < 12; e++) {
             if (c_flexi_edge_patch[code][e] != p) continue;
             const int a = fx_ea[e], b = fx_eb[e];
-            const size_t ga = ((size_t)(i + (a & 1)) * G + (j + ((a >> 1) & 1))) * G + (k + (a >> 2));
-            const size_t gb = ((size_t)(i + (b & 1)) * G + (j + ((b >> 1) & 1))) * G + (k + (b >> 2));
+            const size_t ga = flexi_corner(i, j, k, a, G), gb = flexi_corner(i, j, k, b, G);
             const float D = sc[b] - sc[a];
             float dot = 0.f;
             for (int q = 0; q < 3; q++) dot += g[q] * (xc[3 * a + q] - xc[3 * b + q]);
