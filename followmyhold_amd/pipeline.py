@@ -21,6 +21,8 @@ Differences from the reference, all outside the arithmetic:
     `noise_pred_obj` keeps its own torch AdamW with the same hyper-parameters (Adam is element-wise, so splitting one
     optimiser into two changes nothing).
 """
+import collections
+import contextlib
 import datetime
 import json
 import os
@@ -49,7 +51,6 @@ def vae_attention_backend():
       hip_bwd        = hip (the name of round 5);
       efficient      torch's memory-efficient backend first, the others allowed behind it;
       default        torch's own choice, as the reference runs."""
-    import contextlib
     mode = os.environ.get("FOHO_VAE_SDPA", "hip")
     if mode not in ("efficient", "hip", "hip_bwd", "hip_torch_bwd") or not torch.cuda.is_available():
         return contextlib.nullcontext()
@@ -98,6 +99,13 @@ def latent2sdf(pred, xyz_samples, grid_size, vae, device, num_chunks=8000):
     return -grid_logits.view((1, grid_size[0], grid_size[1], grid_size[2])).float()
 
 
+def _mode(value, env_name, choices, label):
+    """An option switch: `value`, else $`env_name`, else "dense"; one of `choices`."""
+    value = value if value is not None else (os.environ.get(env_name) or "dense")
+    if value not in choices:
+        raise E.L.FohoError(f"{label} {value!r}: one of {choices}")
+    return value
+
 
 FINAL_DECODES = ("dense", "hierarchical")
 
@@ -105,10 +113,7 @@ FINAL_DECODES = ("dense", "hierarchical")
 def final_decode_mode(mode=None):
     """The final decode's mode: `mode`, else $FOHO_FINAL_DECODE, else "dense" (volume.py: "hierarchical" queries the grid only near
     the surface, with a mesh identical to the dense one's for every surface the coarse level sees)."""
-    mode = mode if mode is not None else (os.environ.get("FOHO_FINAL_DECODE") or "dense")
-    if mode not in FINAL_DECODES:
-        raise E.L.FohoError(f"final_decode {mode!r}: one of {FINAL_DECODES}")
-    return mode
+    return _mode(mode, "FOHO_FINAL_DECODE", FINAL_DECODES, "final_decode")
 
 
 FINAL_EXTRACTS = ("dense", "sparse")
@@ -118,10 +123,7 @@ def final_extract_mode(mode=None):
     """The final step's extractor: `mode`, else $FOHO_FINAL_EXTRACT, else "dense" (ops.flexicubes on the dense point grid).  "sparse" is
     sparse_flexi.flexicubes_sparse on per-axis tables: the same mesh bit for bit, and with final_decode="hierarchical" the final
     dense point grid is never built."""
-    mode = mode if mode is not None else (os.environ.get("FOHO_FINAL_EXTRACT") or "dense")
-    if mode not in FINAL_EXTRACTS:
-        raise E.L.FohoError(f"final_extract {mode!r}: one of {FINAL_EXTRACTS}")
-    return mode
+    return _mode(mode, "FOHO_FINAL_EXTRACT", FINAL_EXTRACTS, "final_extract")
 
 
 GUIDANCE_EXTRACTS = ("dense", "sparse")
@@ -131,17 +133,28 @@ def guidance_extract_mode(mode=None):
     """The extractor of the guidance loop's exact-size path: `mode`, else $FOHO_GUIDANCE_EXTRACT, else "dense" (ops.flexicubes on the
     dense point grid).  "sparse" is sparse_flexi.flexicubes_sparse_grad on per-axis tables: the same mesh bit for bit, work and memory
     proportional to the surface cubes, and a dL/dSDF that is bitwise repeatable.  Capacity mode (engine.SdfObjective) is untouched."""
-    mode = mode if mode is not None else (os.environ.get("FOHO_GUIDANCE_EXTRACT") or "dense")
-    if mode not in GUIDANCE_EXTRACTS:
-        raise E.L.FohoError(f"guidance_extract {mode!r}: one of {GUIDANCE_EXTRACTS}")
-    return mode
+    return _mode(mode, "FOHO_GUIDANCE_EXTRACT", GUIDANCE_EXTRACTS, "guidance_extract")
 
 
-def _require_hip_geo(vae):
+GUIDANCE_DECODES = ("dense", "hierarchical")
+
+
+def guidance_decode_mode(mode=None):
+    """How the guidance grid is decoded -- the in-loop decodes of phases B / C and the per-step decodes before the last step: `mode`,
+    else $FOHO_GUIDANCE_DECODE, else "dense".  "hierarchical" is the band decode of latent2sdf_band."""
+    return _mode(mode, "FOHO_GUIDANCE_DECODE", GUIDANCE_DECODES, "guidance_decode")
+
+
+def _require_decoder(vae, which):
+    """vae.hip_geo for the hierarchical decode of the `which` ("final" | "guidance") grid; the guidance grid's band decode runs under
+    autograd and so also needs a backward that does not keep every forward row."""
     hip = getattr(vae, "hip_geo", None)
     if hip is None:
-        raise E.L.FohoError("hierarchical final decode: needs vae.hip_geo, the HIP geometry decoder (geo_decode.install(vae)); the torch module's "
-                            "outputs depend on the batch shape, so decoded subsets would not equal the dense decode")
+        raise E.L.FohoError(f"hierarchical {which} decode: needs vae.hip_geo, the HIP geometry decoder (geo_decode.install(vae)); the torch "
+                            "module's outputs depend on the batch shape, so decoded subsets would not equal the dense decode")
+    if which == "guidance" and hip.backward_mode == "keep":
+        raise E.L.FohoError("hierarchical guidance decode: vae.hip_geo.backward_mode 'keep' keeps the activations of every forward row and "
+                            "cannot serve a band decode: use 'rows' (the default) or 'recompute'")
     return hip
 
 
@@ -164,21 +177,9 @@ def latent2sdf_hierarchical(pred, bmin, bmax, res, vae, device, min_res=None, ba
     -> ((1, G, G, G) float32, negative inside, stats).  Requires `vae.hip_geo`."""
     from . import volume
     volume.check_levels(res, min_res)
-    hip = _require_hip_geo(vae)
+    hip = _require_decoder(vae, "final")
     pred = vae_tokens(vae, 1 / vae.scale_factor * pred)
     return sdf_hierarchical_from_tokens(pred, bmin, bmax, res, hip, min_res=min_res, band=band)
-
-
-GUIDANCE_DECODES = ("dense", "hierarchical")
-
-
-def guidance_decode_mode(mode=None):
-    """How the guidance grid is decoded -- the in-loop decodes of phases B / C and the per-step decodes before the last step: `mode`,
-    else $FOHO_GUIDANCE_DECODE, else "dense".  "hierarchical" is the band decode of latent2sdf_band."""
-    mode = mode if mode is not None else (os.environ.get("FOHO_GUIDANCE_DECODE") or "dense")
-    if mode not in GUIDANCE_DECODES:
-        raise E.L.FohoError(f"guidance_decode {mode!r}: one of {GUIDANCE_DECODES}")
-    return mode
 
 
 def guidance_levels(res, min_res=None):
@@ -188,17 +189,6 @@ def guidance_levels(res, min_res=None):
     from . import volume
     res = int(res)
     return volume.check_levels(res, res // 2 if min_res is None else min_res)
-
-
-def _require_band_decoder(vae):
-    hip = getattr(vae, "hip_geo", None)
-    if hip is None:
-        raise E.L.FohoError("hierarchical guidance decode: needs vae.hip_geo, the HIP geometry decoder (geo_decode.install(vae)); the torch "
-                            "module's outputs depend on the batch shape, so decoded subsets would not equal the dense decode")
-    if hip.backward_mode == "keep":
-        raise E.L.FohoError("hierarchical guidance decode: vae.hip_geo.backward_mode 'keep' keeps the activations of every forward row and "
-                            "cannot serve a band decode: use 'rows' (the default) or 'recompute'")
-    return hip
 
 
 def sdf_band_from_tokens(tokens, xyz_samples, res, hip, bmin, bmax, min_res=None, band=1):
@@ -242,7 +232,7 @@ def latent2sdf_band(pred, xyz_samples, grid_size, vae, device, bmin, bmax, min_r
     The one behavioural difference from latent2sdf: a NaN that the decoder would produce only at points the band fills is not seen."""
     G = int(grid_size[0])
     guidance_levels(G - 1, min_res)
-    hip = _require_band_decoder(vae)
+    hip = _require_decoder(vae, "guidance")
     pred = vae_tokens(vae, 1 / vae.scale_factor * pred)
     sdf, stats, _ = sdf_band_from_tokens([pred], xyz_samples, G - 1, hip, bmin, bmax, min_res=min_res, band=band)
     return sdf.view(1, G, G, G), stats[0]
@@ -282,6 +272,19 @@ def _check_rows_dropped(hip):
                                 "is incomplete (raise obj_capacity or leave vae.hip_geo.row_cap = None)")
 
 
+@contextlib.contextmanager
+def _latent_phase_scope(hip):
+    """One latent phase (B / C) of either driver on the shared decoder `hip` (vae.hip_geo, or None).  However the phase ends -- a NaN
+    return, an exception --, neither the active-row bound nor a dropped-row count outlives it: the count of a phase that never reached
+    its own _check_rows_dropped must not fail the next phase's."""
+    try:
+        yield
+    finally:
+        if hip is not None:
+            hip.row_cap = None
+            hip.take_rows_dropped()
+
+
 def similarity_about_center(verts, scale, quat, trans):
     """transform_mesh_around_center_w_scale (PL:108-118): scale and rotate about the bounding-box centre, then shift."""
     center = (verts.min(dim=0)[0] + verts.max(dim=0)[0]) / 2.0
@@ -303,6 +306,175 @@ class BatchLeftFastPath(RuntimeError):
     def __init__(self, msg, phase=None, step=None, iteration=None, flags=0):
         super().__init__(msg)
         self.phase, self.step, self.iteration, self.flags = phase, step, iteration, flags
+
+
+# ---------------------------------------------------------------------- what `__call__` and `call_batch` share
+_Options = collections.namedtuple("_Options", "final_mode final_min_res final_sparse guid_band guid_min_res")
+_OPTION_KWARGS = ("final_decode", "final_decode_min_res", "final_extract", "guidance_decode", "guidance_decode_min_res")
+_Schedule = collections.namedtuple("_Schedule", "do_cfg cond bmin bmax xyz timesteps n_steps_obj guidance")
+
+
+def _schedule_options(vae, guid_res, final_res, final_decode, final_decode_min_res, final_extract, guidance_decode, guidance_decode_min_res):
+    """The drivers' option switches (arguments in the order of _OPTION_KWARGS), parsed and then validated against the grids and the VAE:
+    a bad one is refused before any work, not after the whole schedule."""
+    final_mode = final_decode_mode(final_decode)
+    final_sparse = final_extract_mode(final_extract) == "sparse"
+    guid_band = guidance_decode_mode(guidance_decode) == "hierarchical"
+    if final_mode == "hierarchical":
+        from . import volume
+        volume.check_levels(final_res, final_decode_min_res)
+        _require_decoder(vae, "final")
+    if guid_band:
+        guidance_levels(guid_res, guidance_decode_min_res)
+        _require_decoder(vae, "guidance")
+    return _Options(final_mode, final_decode_min_res, final_sparse, guid_band, guidance_decode_min_res)
+
+
+def _grid_points(bmin, bmax, res, device):
+    """The dense point grid the latent is decoded on (PL:1126-1143); FlexiCubes needs no cube index table here."""
+    xyz_np, _, _ = generate_dense_grid_points(bmin, bmax, octree_depth=5, octree_resolution=res, indexing="ij")
+    return torch.as_tensor(xyz_np, dtype=torch.float32, device=device)
+
+
+def _load_scenes(paths, fovs, J_regressor, device):
+    """Per-image inputs (PL:1217-1256): masks, keypoints, aligned MANO mesh, Hunyuan -> MoGe transform, MoGe target maps.  paths: per image
+    a dict with the reference's eight path names (fov.json lies next to the MoGe mesh); fovs: per image degrees, or None for its fov.json;
+    J_regressor: None for the file of PL:1218.  -> (scenes, T_h2m, hand_verts, hand_faces), the last three per image on the device."""
+    jr = inputs.load_j_regressor() if J_regressor is None else np.asarray(J_regressor, np.float32)
+    scenes = []
+    for p, fov in zip(paths, fovs):
+        q = dict(cropped_hand_mask_path=p["hand_mask_path"], cropped_obj_mask_path=p["obj_mask_path"], moge_mesh_path=p["moge_mesh_path"],
+                 moge_fov_path=os.path.join(os.path.dirname(p["moge_mesh_path"]), "fov.json"), T_h2m_path=p["h2m_rt_path"],
+                 aligned_mano_mesh_path=p["aligned_mano_mesh_path"], hamer_for_guid_path=p["hamer_for_guid_path"])
+        scenes.append(inputs.load_scene_from_files(q, jr, E.hip_render_fn(device), fov=fov, with_object=False))
+    on_device = lambda key, dtype: [torch.as_tensor(sc[key], dtype=dtype, device=device) for sc in scenes]
+    return scenes, on_device("T_h2m", torch.float32), on_device("hand_verts", torch.float32), on_device("hand_faces", torch.int64)
+
+
+def _hand_phase(gb, cfg0, i, stats, device, spg=None, after_capture=None, before_replay=None):
+    """Phase A: hands only, no latent involved (PL:1296-1358): optimization_steps_hand fused steps as replays of one captured graph of
+    `spg` steps (default: the largest divisor of the count up to 50).  after_capture() runs between the capture and the first replay,
+    before_replay(rep) in front of each replay.  -> the flags raise_on_flags returns."""
+    cfg, n_renders = E.phase_cfg("A", cfg0, denoise_i=i, do_update=True)
+    gb.set_n_renders(n_renders)
+    gb.reset_optimizer()
+    n = int(cfg0.optimization_steps_hand)
+    if spg is None:
+        spg = max([d for d in range(1, 51) if n % d == 0]) if n > 0 else 1
+    graph = gb.capture(cfg, steps_per_graph=spg)
+    if after_capture is not None:
+        after_capture()
+    gb.reset_optimizer()
+    for rep in range(n // spg):
+        if before_replay is not None:
+            before_replay(rep)
+        graph.replay()
+    stats["inner_iterations"] += n
+    torch.cuda.synchronize(device)
+    return gb.raise_on_flags(strict_k=False)
+
+
+class _StepDecoder:
+    """Every decode of one driver call, at the level of VAE tokens: `vae_tokens` runs once for all images of the call, then each live image
+    goes through the HIP decoder (gradients through foho_geo_decode_bwd) or through the torch module in chunks of `num_chunks` queries; a
+    frozen slot (`frozen`: call_batch's images that left the batch) is not decoded any more and gets the all-ones field: no surface.  An
+    image's values are those latent2sdf, latent2sdf_band and latent2sdf_hierarchical compute for it.  Fills stats["guidance_decode"],
+    stats["final_decode"] and stats["final_extract"]: one entry for `__call__`, a list per image for call_batch (`per_image`)."""
+
+    def __init__(self, vae, sch, opts, guid_res, final_res, stats, num_chunks, n_images=1, frozen=(), per_image=False):
+        self.vae, self.sch, self.opts, self.guid_res, self.final_res, self.stats = vae, sch, opts, guid_res, final_res, stats
+        self.num_chunks, self.n_images, self.frozen, self.per_image = num_chunks, n_images, frozen, per_image
+
+    def _open(self, key):
+        if self.per_image:
+            self.stats[key] = [None] * self.n_images
+
+    def _record(self, key, b, value):
+        if self.per_image:
+            self.stats[key][b] = value
+        else:
+            self.stats[key] = value
+
+    def guidance(self, x1):
+        """The fields of latents x1 (B, ...) on the guidance grid, a list of B ((guid_res+1)^3,) tensors: dense, or the band decode with
+        the live images in lockstep (sdf_band_from_tokens), either with or without gradient."""
+        return self._fields(x1, self.guid_res, self.sch.xyz, "band" if self.opts.guid_band else "dense")
+
+    def step_grid(self, last):
+        """The grid a step's clean-sample estimate is decoded on and its extractor -> (res, points or None, extract(field, b) -> (verts,
+        faces)): the guidance grid before the last step (those meshes only matter as the fall-back of a later empty decode), the final
+        grid at the last one (PL:1626-1642) -- whose points neither a hierarchical decode nor the sparse extractor reads."""
+        sch, opts = self.sch, self.opts
+        res = self.final_res if last else self.guid_res
+        sparse = last and opts.final_sparse
+        if res == self.guid_res:
+            xyz = sch.xyz
+        else:
+            xyz = None if sparse and opts.final_mode == "hierarchical" else _grid_points(sch.bmin, sch.bmax, res, sch.xyz.device)
+        if not sparse:
+            return res, xyz, lambda s, b: ops.flexicubes(xyz, s, res)[:2]
+        axes = ops.grid_axes(sch.bmin, sch.bmax, res).to(sch.xyz.device)      # the final step's mesh from axis tables
+        self._open("final_extract")
+
+        def extract(s, b):
+            v, f, _, st = ops.flexicubes_sparse(axes, s, res, return_stats=True)
+            self._record("final_extract", b, st)
+            return v, f
+
+        return res, xyz, extract
+
+    def step(self, x1, last, res, xyz):
+        """The fields of a step's clean-sample estimates x1 on step_grid(last)'s grid, a list of B ((res+1)^3,) tensors without gradient:
+        the last step's dense or near the surface only (volume.py), an earlier step's as guidance() decodes."""
+        if last:
+            return self._fields(x1, res, xyz, "hierarchical" if self.opts.final_mode == "hierarchical" else "dense")
+        return self.guidance(x1)
+
+    def _fields(self, x1, res, xyz, mode):
+        vae, sch, hip = self.vae, self.sch, getattr(self.vae, "hip_geo", None)
+        tokens = vae_tokens(vae, 1 / vae.scale_factor * x1)          # all images through ONE foho_vae_fwd (rows = images x tokens)
+        n = (res + 1) ** 3
+        live = [b for b in range(x1.shape[0]) if b not in self.frozen]
+        out = [torch.ones(n, device=x1.device) if b in self.frozen else None for b in range(x1.shape[0])]
+        if mode == "band":
+            sdf, sts, _ = sdf_band_from_tokens([tokens[b:b + 1] for b in live], xyz, res, hip, sch.bmin, sch.bmax, min_res=self.opts.guid_min_res)
+            for j, b in enumerate(live):
+                out[b] = sdf[j]
+                _tally(self.stats["guidance_decode"][b] if self.per_image else self.stats["guidance_decode"], sts[j])
+        elif mode == "hierarchical":
+            self._open("final_decode")
+            for b in live:
+                sdf_b, st = sdf_hierarchical_from_tokens(tokens[b:b + 1], sch.bmin, sch.bmax, res, hip, min_res=self.opts.final_min_res)
+                out[b] = sdf_b.view(-1)
+                self._record("final_decode", b, st)
+        else:
+            for b in live:
+                if hip is not None:          # geo_decode.install(vae): all grid points in one call, fp16 query points like PL:303
+                    out[b] = -hip(hip.grid_queries(xyz), tokens[b:b + 1]).view(-1).float()
+                    continue
+                logits = [vae.geo_decoder(xyz[s0:s0 + self.num_chunks].half().unsqueeze(0), tokens[b:b + 1]) for s0 in range(0, n, self.num_chunks)]
+                out[b] = -torch.cat(logits, dim=1).view(-1).float()
+        return out
+
+
+def _single_colour(verts, faces, channel):
+    tex = torch.zeros_like(verts)
+    tex[:, channel] = 1.0
+    return Meshes(verts=[verts], faces=[faces], textures=TexturesVertex(verts_features=[tex]))
+
+
+def _meshes_in_moge_world(verts, faces, T_h2m, p, hand_verts, hand_faces, with_hand):
+    """A step's clean-sample estimate in the MoGe world (PL:1612-1661) from the extracted mesh, the Hunyuan -> MoGe transform, the 16
+    similarity parameters `p` and the MoGe-space MANO mesh -> (blue object Meshes, or None for an empty mesh; green hand Meshes, or None
+    without `with_hand`).  The hand is THIS step's whatever the decode gives: PL:1615-1619 come before the empty-mesh test of PL:1644-1646."""
+    obj = hand = None
+    if with_hand:
+        hand = _single_colour(similarity_about_center(hand_verts, p[0], p[4:8], p[1:4]), hand_faces, 1)
+    if verts.shape[0] == 0:
+        print("Invalid mesh detected, aborting step!")
+    else:
+        obj = _single_colour(similarity_about_center(verts @ T_h2m[:3, :3].T + T_h2m[:3, 3], p[8], p[12:16], p[9:12]), faces, 2)
+    return obj, hand
 
 
 class GuidedShapePipeline:
@@ -391,6 +563,36 @@ class GuidedShapePipeline:
         masks = torch.cat(masks, dim=0).to(self.device, dtype=self.dtype) if masks[0] is not None else None
         return images, masks
 
+    # ------------------------------------------------------------------ the schedule both drivers run
+    def _schedule_setup(self, images, guidance_scale, n_images, n_steps, guid_res, sigmas=None):
+        """What the denoising loop needs besides latents and scenes (PL:1100-1215): the conditioning, the guidance grid over the Hunyuan
+        box, the timesteps (sigmas start from 0, PL:1186-1193) and the guidance tensor; the networks in eval mode."""
+        do_cfg = guidance_scale >= 0 and not (getattr(self.model, "guidance_embed", False) is True)
+        img, msk = self.prepare_image(images)
+        cond = self.encode_cond(image=img, mask=msk, do_classifier_free_guidance=do_cfg, dual_guidance=False)
+        bmin, bmax = np.full(3, -1.10), np.full(3, 1.10)
+        xyz = _grid_points(bmin, bmax, guid_res, self.device)
+        sigmas = np.linspace(0, 1, n_steps) if sigmas is None else sigmas
+        timesteps, n_steps_obj = retrieve_timesteps(self.scheduler, n_steps, self.device, sigmas=sigmas)
+        guidance = None
+        if getattr(self.model, "guidance_embed", False) is True:
+            guidance = torch.tensor([guidance_scale] * n_images, device=self.device, dtype=self.dtype)
+        self.model.eval()
+        self.vae.eval()
+        return _Schedule(do_cfg, cond, bmin, bmax, xyz, timesteps, n_steps_obj, guidance)
+
+    def _noise_prediction(self, sch, latents, i, t, cfg0):
+        """The DiT's noise prediction at step i, with the classifier-free mix: trust the learned prior early, the guidance later
+        (PL:1284-1293)."""
+        latent_in = torch.cat([latents] * 2) if sch.do_cfg else latents
+        timestep = t.expand(latent_in.shape[0]).to(latents.dtype) / self.scheduler.config.num_train_timesteps
+        noise_pred = self.model(latent_in, timestep, sch.cond, guidance=sch.guidance)
+        if sch.do_cfg:
+            scale_i = cfg0.obj_guidance_scale * (1 - i / sch.n_steps_obj) if i >= cfg0.guidance_start_step + 1 else cfg0.obj_guidance_scale
+            c, u = noise_pred.chunk(2)
+            noise_pred = u + scale_i * (c - u)
+        return noise_pred
+
     # ------------------------------------------------------------------ B images through one pass of the schedule
     @torch.no_grad()
     def call_batch(self, images, paths, generators=None, guidance_scale=7.5, num_chunks=8000, config=None, renderer=None,
@@ -424,114 +626,33 @@ class GuidedShapePipeline:
         by ops.flexicubes on the dense point grid or by flexicubes_sparse on axis tables (the same mesh; with a hierarchical final
         decode the final point grid is not built); per-image stats in stats["final_extract"]."""
         B = len(images)
-        final_mode = final_decode_mode(final_decode)
-        final_sparse = final_extract_mode(final_extract) == "sparse"
-        if final_mode == "hierarchical":
-            from . import volume
-            volume.check_levels(final_octree_resolution, final_decode_min_res)
-            _require_hip_geo(self.vae)
-        guid_band = guidance_decode_mode(guidance_decode) == "hierarchical"
-        if guid_band:
-            guidance_levels(guidance_octree_resolution, guidance_decode_min_res)
-            _require_band_decoder(self.vae)
+        guid_res, final_res = int(guidance_octree_resolution), int(final_octree_resolution)
+        opts = _schedule_options(self.vae, guid_res, final_res, final_decode, final_decode_min_res, final_extract, guidance_decode,
+                                 guidance_decode_min_res)
         device, dtype = self.device, self.dtype
         cfg0 = config() if config is not None else E.OptimizationConfig()
         self.stats = stats = {"inner_iterations": 0, "images": B, "skipped_empty": 0}
-        if guid_band:
+        if opts.guid_band:
             stats["guidance_decode"] = [{} for _ in range(B)]
         left = {}                 # image -> BatchLeftFastPath: frozen slots
-        do_cfg = guidance_scale >= 0 and not (getattr(self.model, "guidance_embed", False) is True)
-        img, msk = self.prepare_image(list(images))
-        cond = self.encode_cond(image=img, mask=msk, do_classifier_free_guidance=do_cfg, dual_guidance=False)
-        guid_res = int(guidance_octree_resolution)
-        bmin, bmax = np.full(3, -1.10), np.full(3, 1.10)
-
-        def grid(res):
-            xyz_np, gsz, _ = generate_dense_grid_points(bmin, bmax, octree_depth=5, octree_resolution=res, indexing="ij")
-            return torch.as_tensor(xyz_np, dtype=torch.float32, device=device), gsz
-
-        xyz_samples, grid_size = grid(guid_res)
-        n_steps = cfg0.num_inference_steps
-        timesteps, n_steps_obj = retrieve_timesteps(self.scheduler, n_steps, device, sigmas=np.linspace(0, 1, n_steps))
-        guidance = None
-        if getattr(self.model, "guidance_embed", False) is True:
-            guidance = torch.tensor([guidance_scale] * B, device=device, dtype=dtype)
-        self.model.eval()
-        self.vae.eval()
+        n_steps, hand_start = cfg0.num_inference_steps, cfg0.handopt_start_step
+        sch = self._schedule_setup(list(images), guidance_scale, B, n_steps, guid_res)
         if generators is None:
             generators = [torch.Generator().manual_seed(2) for _ in range(B)]
         latents = torch.cat([self.prepare_latents(1, dtype, device, g) for g in generators], 0).clone()
 
         if fovs is None:
             fovs = [float(renderer.rasterizer.cameras.fov) if renderer is not None else None] * B
-        jr = inputs.load_j_regressor() if J_regressor is None else np.asarray(J_regressor, np.float32)
-        scenes = []
-        for p_, fov in zip(paths, fovs):
-            q = dict(cropped_hand_mask_path=p_["hand_mask_path"], cropped_obj_mask_path=p_["obj_mask_path"], moge_mesh_path=p_["moge_mesh_path"],
-                     moge_fov_path=os.path.join(os.path.dirname(p_["moge_mesh_path"]), "fov.json"), T_h2m_path=p_["h2m_rt_path"],
-                     aligned_mano_mesh_path=p_["aligned_mano_mesh_path"], hamer_for_guid_path=p_["hamer_for_guid_path"])
-            scenes.append(inputs.load_scene_from_files(q, jr, E.hip_render_fn(device), fov=fov, with_object=False))
+        scenes, T_h2m, hand_moge, hand_faces = _load_scenes(paths, fovs, J_regressor, device)
         cap = tuple(obj_capacity) if obj_capacity else (8 * guid_res * guid_res, 16 * guid_res * guid_res)
         gb = E.GuidanceBatch(scenes, device=device, grid_res=guid_res, n_renders=2, obj_capacity=cap)
-        fobj = E.SdfObjective(gb, xyz_samples, guid_res)
+        fobj = E.SdfObjective(gb, sch.xyz, guid_res)
         hip_dec = getattr(self.vae, "hip_geo", None)
-        T_h2m = [torch.as_tensor(sc["T_h2m"], dtype=torch.float32, device=device) for sc in scenes]
-        hand_moge = [torch.as_tensor(sc["hand_verts"], dtype=torch.float32, device=device) for sc in scenes]
-        hand_faces = [torch.as_tensor(sc["hand_faces"], dtype=torch.int64, device=device) for sc in scenes]
-
-        def sdf_of(x1, xyz, gsz):
-            """latent2sdf (PL:292-313) for B latents: the VAE transformer on all of them, the geometry decoder per image."""
-            pred = vae_tokens(self.vae, 1 / self.vae.scale_factor * x1)      # all images through ONE foho_vae_fwd (rows = images x tokens)
-            out = []
-            hip = getattr(self.vae, "hip_geo", None)
-            for b in range(x1.shape[0]):
-                if b in left:                # a frozen slot is not decoded any more (an all-positive field: no surface)
-                    out.append(torch.ones(xyz.shape[0], device=device))
-                    continue
-                if hip is not None:          # geo_decode.install(vae): all points in one call, gradients through foho_geo_decode_bwd
-                    out.append(-hip(hip.grid_queries(xyz), pred[b:b + 1]).view(-1).float())
-                    continue
-                logits = [self.vae.geo_decoder(xyz[s0:s0 + num_chunks].half().unsqueeze(0), pred[b:b + 1]) for s0 in range(0, xyz.shape[0], num_chunks)]
-                out.append(-torch.cat(logits, dim=1).view(-1).float())
-            return torch.stack(out, 0)
-
-        def sdf_band_of(x1):
-            """sdf_of on the guidance grid by the band decode: the VAE transformer on all images as sdf_of runs it, the images that are
-            still in the batch through the levels in lockstep."""
-            pred = vae_tokens(self.vae, 1 / self.vae.scale_factor * x1)
-            live = [b for b in range(x1.shape[0]) if b not in left]
-            out = [torch.ones(xyz_samples.shape[0], device=device) for _ in range(x1.shape[0])]
-            sdf, sts, _ = sdf_band_from_tokens([pred[b:b + 1] for b in live], xyz_samples, guid_res, hip_dec, bmin, bmax,
-                                               min_res=guidance_decode_min_res)
-            for j, b in enumerate(live):
-                out[b] = sdf[j]
-                _tally(stats["guidance_decode"][b], sts[j])
-            return torch.stack(out, 0)
-
-        def final_sdf_hierarchical(x1, res):
-            """sdf_of's fields for the final step by the hierarchical decode: the VAE transformer on all images as sdf_of runs it, the
-            decoder near each image's surface only (volume.py)."""
-            pred = vae_tokens(self.vae, 1 / self.vae.scale_factor * x1)
-            out, stats["final_decode"] = [], [None] * B
-            for b in range(B):
-                if b in left:
-                    out.append(torch.ones((res + 1) ** 3, device=device))
-                    continue
-                sdf_b, stats["final_decode"][b] = sdf_hierarchical_from_tokens(pred[b:b + 1], bmin, bmax, res, hip_dec,
-                                                                                min_res=final_decode_min_res)
-                out.append(sdf_b.view(-1))
-            return torch.stack(out, 0)
+        decoder = _StepDecoder(self.vae, sch, opts, guid_res, final_res, stats, num_chunks, n_images=B, frozen=left, per_image=True)
 
         LEAVE, EMPTY = 1 | 16 | 32, 64      # flag bits: NaN loss, capacity overflow, not a closed manifold | empty iso-surface
 
         def latent_phase(phase, iters, i, t, noise_pred, lr):
-            try:
-                return latent_phase_body(phase, iters, i, t, noise_pred, lr)
-            finally:          # however the phase ends (an exception included), the shared decoder's active-row bound does not outlive it
-                if hip_dec is not None:
-                    hip_dec.row_cap = None
-
-        def latent_phase_body(phase, iters, i, t, noise_pred, lr):
             cfg, n_renders = E.phase_cfg(phase, cfg0, denoise_i=i, do_update=True)
             gb.set_n_renders(n_renders)
             gb.reset_optimizer()
@@ -543,8 +664,7 @@ class GuidedShapePipeline:
             opt = torch.optim.AdamW([{"params": [n], "lr": lr} for n in noise], eps=1e-4)
             for k in range(int(iters)):
                 opt.zero_grad(set_to_none=True)
-                x1 = self.scheduler.step_final(torch.cat(noise, 0), t, latents)
-                sdf = sdf_band_of(x1) if guid_band else sdf_of(x1, xyz_samples, grid_size)
+                sdf = torch.stack(decoder.guidance(self.scheduler.step_final(torch.cat(noise, 0), t, latents)), 0)
                 loss = fobj(sdf, cfg)                                   # (B,): one replay for all images
                 fl = gb.flags.cpu().tolist()                            # the iteration's read-back (NaN is bit 0 of the flags) ...
                 if hip_dec is not None:                                 # ... with the rows the decoder's backward will find a gradient on
@@ -576,79 +696,29 @@ class GuidedShapePipeline:
             _check_rows_dropped(hip_dec)
             return torch.cat([n.detach() for n in noise], 0).clone()
 
-        results = [None] * B
-        for i, t in enumerate(timesteps):
-            latent_in = torch.cat([latents] * 2) if do_cfg else latents
-            timestep = t.expand(latent_in.shape[0]).to(latents.dtype) / self.scheduler.config.num_train_timesteps
-            noise_pred = self.model(latent_in, timestep, cond, guidance=guidance)
-            if do_cfg:
-                scale_i = cfg0.obj_guidance_scale * (1 - i / n_steps_obj) if i >= cfg0.guidance_start_step + 1 else cfg0.obj_guidance_scale
-                c, u = noise_pred.chunk(2)
-                noise_pred = u + scale_i * (c - u)
-            if i >= cfg0.handopt_start_step:
+        results = [(None, None)] * B
+        for i, t in enumerate(sch.timesteps):
+            noise_pred = self._noise_prediction(sch, latents, i, t, cfg0)
+            if i >= hand_start:
                 with torch.enable_grad():
-                    if i == cfg0.handopt_start_step:                     # phase A: hands only (PL:1296-1358)
-                        cfg, n_renders = E.phase_cfg("A", cfg0, denoise_i=i, do_update=True)
-                        gb.set_n_renders(n_renders)
-                        gb.reset_optimizer()
-                        n = int(cfg0.optimization_steps_hand)
-                        spg = max([d for d in range(1, 51) if n % d == 0]) if n > 0 else 1
-                        graph = gb.capture(cfg, steps_per_graph=spg)
-                        gb.reset_optimizer()
-                        for _ in range(n // spg):
-                            graph.replay()
-                        stats["inner_iterations"] += n
-                        torch.cuda.synchronize(device)
-                        gb.raise_on_flags(strict_k=False)
-                    elif len(left) == B:
-                        pass                                             # nobody left to optimise: the caller re-runs them all
-                    elif i == cfg0.handopt_start_step + 1:               # phase B (PL:1361-1453)
-                        noise_pred = latent_phase("B", cfg0.optimization_steps_scale, i, t, noise_pred, cfg0.noise_obj_lr1)
-                    else:                                                # phase C (PL:1455-1601)
-                        noise_pred = latent_phase("C", cfg0.optimization_steps_joint, i, t, noise_pred, cfg0.noise_obj_lr2)
+                    if i == hand_start:
+                        _hand_phase(gb, cfg0, i, stats, device)
+                    elif len(left) < B:                                  # (else nobody is left to optimise: the caller re-runs them all)
+                        with _latent_phase_scope(hip_dec):
+                            if i == hand_start + 1:                      # phase B (PL:1361-1453)
+                                noise_pred = latent_phase("B", cfg0.optimization_steps_scale, i, t, noise_pred, cfg0.noise_obj_lr1)
+                            else:                                        # phase C (PL:1455-1601)
+                                noise_pred = latent_phase("C", cfg0.optimization_steps_joint, i, t, noise_pred, cfg0.noise_obj_lr2)
                 noise_pred = noise_pred.detach().clone()
             latents = self.scheduler.step(noise_pred, t, latents).prev_sample
-            # the clean-sample estimate as a mesh in the MoGe world (PL:1612-1661): the last one is the result; earlier ones
-            # only matter as the fall-back of a later empty decode, so they are taken on the guidance grid
-            res = final_octree_resolution if i == n_steps - 1 else guid_res
-            sparse = final_sparse and i == n_steps - 1
-            if res == guid_res:
-                xyz_d, gsz_d = xyz_samples, grid_size
-            elif sparse and final_mode == "hierarchical":        # neither the decode nor the extractor reads the dense point grid
-                xyz_d, gsz_d = None, None
-            else:
-                xyz_d, gsz_d = grid(res)
-            if sparse:
-                axes_d = ops.grid_axes(bmin, bmax, res).to(device)
-                stats["final_extract"] = [None] * B
-            if i == n_steps - 1 and final_mode == "hierarchical":
-                sdf = final_sdf_hierarchical(self.scheduler.step_final(noise_pred, t, latents), res)
-            elif i < n_steps - 1 and guid_band:
-                sdf = sdf_band_of(self.scheduler.step_final(noise_pred, t, latents))
-            else:
-                sdf = sdf_of(self.scheduler.step_final(noise_pred, t, latents), xyz_d, gsz_d)
+            # the clean-sample estimate as a mesh in the MoGe world (PL:1612-1661): the last one is the result
+            last = i == n_steps - 1
+            res, xyz, extract = decoder.step_grid(last)
+            sdf = decoder.step(self.scheduler.step_final(noise_pred, t, latents), last, res, xyz)
             for b in range(B):
-                if b in left:
-                    continue
-                p = gb.params[b]
-                obj, hand = results[b] if results[b] is not None else (None, None)
-                if i >= cfg0.handopt_start_step:         # the hand of THIS step, whatever the decode gives (PL:1615-1619 come before the
-                    hv = similarity_about_center(hand_moge[b], p[0], p[4:8], p[1:4])       # empty-mesh test of PL:1644-1646)
-                    tex_h = torch.zeros_like(hv)
-                    tex_h[:, 1] = 1.0
-                    hand = Meshes(verts=[hv], faces=[hand_faces[b]], textures=TexturesVertex(verts_features=[tex_h]))
-                if sparse:
-                    verts, faces, _, stats["final_extract"][b] = ops.flexicubes_sparse(axes_d, sdf[b], res, return_stats=True)
-                else:
-                    verts, faces, _ = ops.flexicubes(xyz_d, sdf[b], res)
-                if verts.shape[0] == 0:
-                    print("Invalid mesh detected, aborting step!")
-                else:
-                    obj_world = similarity_about_center(verts @ T_h2m[b][:3, :3].T + T_h2m[b][:3, 3], p[8], p[12:16], p[9:12])
-                    tex = torch.zeros_like(obj_world)
-                    tex[:, 2] = 1.0
-                    obj = Meshes(verts=[obj_world], faces=[faces], textures=TexturesVertex(verts_features=[tex]))
-                results[b] = (obj, hand)
+                if b not in left:
+                    obj, hand = _meshes_in_moge_world(*extract(sdf[b], b), T_h2m[b], gb.params[b], hand_moge[b], hand_faces[b], i >= hand_start)
+                    results[b] = (results[b][0] if obj is None else obj, results[b][1] if hand is None else hand)
         for b, why in left.items():
             results[b] = why
         self.guidance_batch = gb
@@ -666,28 +736,15 @@ class GuidedShapePipeline:
         kwargs.pop("callback", None)            # popped and ignored, as in PL:1073-1074
         kwargs.pop("callback_steps", None)
         final_res = int(kwargs.pop("final_octree_resolution", 384))          # PL:1627 (tests use a smaller grid)
-        # "dense" (default) | "hierarchical": how the final-step grid is decoded (volume.py); not in the signature, which is the reference's
-        final_mode = final_decode_mode(kwargs.pop("final_decode", None))
-        final_min_res = kwargs.pop("final_decode_min_res", None)
-        if final_mode == "hierarchical":                  # refused before any work, not after the whole schedule
-            from . import volume
-            volume.check_levels(final_res, final_min_res)
-            _require_hip_geo(self.vae)
-        # "dense" (default) | "sparse": the final step's extractor (final_extract_mode); not in the signature either
-        final_sparse = final_extract_mode(kwargs.pop("final_extract", None)) == "sparse"
-        # "dense" (default) | "sparse": the extractor of the guidance loop's exact-size path (guidance_extract_mode); not in the signature either
+        guid_res = int(kwargs.pop("guidance_octree_resolution", 64))
+        # not in the signature, which is the reference's: call_batch's final_decode (+ _min_res), final_extract and guidance_decode (+ _min_res),
+        # and "dense" (default) | "sparse", the extractor of the guidance loop's exact-size path (guidance_extract_mode)
+        opts = _schedule_options(self.vae, guid_res, final_res, *[kwargs.pop(k, None) for k in _OPTION_KWARGS])
         guid_sparse = guidance_extract_mode(kwargs.pop("guidance_extract", None)) == "sparse"
-        # "dense" (default) | "hierarchical": how the guidance grid is decoded (latent2sdf_band), with guidance_decode_min_res; not in the
-        # signature either
-        guid_band = guidance_decode_mode(kwargs.pop("guidance_decode", None)) == "hierarchical"
-        guid_min_res = kwargs.pop("guidance_decode_min_res", None)
-        if guid_band:
-            guidance_levels(kwargs.get("guidance_octree_resolution", 64), guid_min_res)
-            _require_band_decoder(self.vae)
         J_regressor = kwargs.pop("J_regressor", None)                        # default: the file of PL:1218
         on_phase_end = kwargs.pop("on_phase_end", None)      # hook(phase, denoising step, GuidanceBatch): inspection / tests
         self.stats = stats = {"inner_iterations": 0, "skipped_empty": 0}
-        if guid_band:
+        if opts.guid_band:
             stats["guidance_decode"] = {}
         if guid_sparse:
             stats["guidance_extract"] = {"calls": 0, "cubes": 0, "vertices": 0, "faces": 0}
@@ -709,22 +766,8 @@ class GuidedShapePipeline:
                 log.write(msg + "\n")
             print(msg)
 
-        do_cfg = guidance_scale >= 0 and not (getattr(self.model, "guidance_embed", False) is True)
-        obj_img, obj_mask = self.prepare_image(image)
-        cond_obj = self.encode_cond(image=obj_img, mask=obj_mask, do_classifier_free_guidance=do_cfg, dual_guidance=False)
-
-        # dense grid the latent is decoded on (PL:1126-1143); FlexiCubes needs no cube index table here
-        octree_res = 64 if "guidance_octree_resolution" not in kwargs else int(kwargs.pop("guidance_octree_resolution"))
-        guid_res = octree_res
-        bmin, bmax = np.full(3, -1.10), np.full(3, 1.10)
-        xyz_np, grid_size, _ = generate_dense_grid_points(bmin, bmax, octree_depth=5, octree_resolution=octree_res, indexing="ij")
-        xyz_samples = torch.as_tensor(xyz_np, dtype=torch.float32, device=device)
-
-        obj_guidance_scale = cfg0.obj_guidance_scale
-        batch_size = cfg0.batch_size
         num_inference_steps = cfg0.num_inference_steps
         handopt_start_step = cfg0.handopt_start_step
-        guidance_start_step = cfg0.guidance_start_step
         guidance_end_step = num_inference_steps
         if debug_root:
             keys = ["obj_guidance_scale", "optimization_steps_hand", "optimization_steps_joint", "optimization_steps_scale",
@@ -733,47 +776,17 @@ class GuidedShapePipeline:
             with open(os.path.join(save_dir, "params.json"), "w") as f:
                 json.dump({**{k: getattr(cfg0, k) for k in keys}, "guidance_end_step": guidance_end_step}, f, indent=4)
 
-        sigmas = np.linspace(0, 1, num_inference_steps) if sigmas is None else sigmas     # starts from 0 (PL:1186-1193)
-        timesteps_obj, n_steps_obj = retrieve_timesteps(self.scheduler, num_inference_steps, device, sigmas=sigmas)
-        guidance = None
-        if getattr(self.model, "guidance_embed", False) is True:
-            guidance = torch.tensor([guidance_scale] * batch_size, device=device, dtype=dtype)
-        self.model.eval()
-        self.vae.eval()
-        obj_latents = self.prepare_latents(batch_size, dtype, device, generator).clone()
+        sch = self._schedule_setup(image, guidance_scale, cfg0.batch_size, num_inference_steps, guid_res, sigmas=sigmas)
+        xyz_samples, bmin, bmax = sch.xyz, sch.bmin, sch.bmax
+        obj_latents = self.prepare_latents(cfg0.batch_size, dtype, device, generator).clone()
 
-        # per-image inputs (PL:1217-1256): masks, keypoints, aligned MANO mesh, Hunyuan -> MoGe transform, MoGe target maps
         fov = float(renderer.rasterizer.cameras.fov) if renderer is not None else None
-        paths = dict(cropped_hand_mask_path=hand_mask_path, cropped_obj_mask_path=obj_mask_path, moge_mesh_path=moge_mesh_path,
-                     moge_fov_path=os.path.join(os.path.dirname(moge_mesh_path), "fov.json"), T_h2m_path=h2m_rt_path,
+        paths = dict(hand_mask_path=hand_mask_path, obj_mask_path=obj_mask_path, moge_mesh_path=moge_mesh_path, h2m_rt_path=h2m_rt_path,
                      aligned_mano_mesh_path=aligned_mano_mesh_path, hamer_for_guid_path=hamer_for_guid_path)
-        jr = inputs.load_j_regressor() if J_regressor is None else np.asarray(J_regressor, np.float32)
-        scene = inputs.load_scene_from_files(paths, jr, E.hip_render_fn(device), fov=fov, with_object=False)
+        (scene,), (T_h2m,), (hand_moge,), (hand_faces,) = _load_scenes([paths], [fov], J_regressor, device)
         gb = E.GuidanceBatch([scene], device=device, grid_res=guid_res, n_renders=2)
-        T_h2m = torch.as_tensor(scene["T_h2m"], dtype=torch.float32, device=device)
-        hand_moge = torch.as_tensor(scene["hand_verts"], dtype=torch.float32, device=device)
-        hand_faces = torch.as_tensor(scene["hand_faces"], dtype=torch.int64, device=device)
-
-        def guidance_sdf(x1):
-            """latent2sdf on the guidance grid, by the band decode when guidance_decode is "hierarchical"."""
-            if not guid_band:
-                return latent2sdf(x1, xyz_samples, grid_size, self.vae, device, num_chunks)
-            sdf, st = latent2sdf_band(x1, xyz_samples, grid_size, self.vae, device, bmin, bmax, min_res=guid_min_res)
-            _tally(stats["guidance_decode"], st)
-            return sdf
-
-        def decode_mesh(noise_pred, t, latents, res, xyz, gsz, hierarchical=False, band=False, sparse=False):
-            x1 = self.scheduler.step_final(noise_pred, t, latents)
-            if hierarchical:          # the final step's grid queried near the surface only
-                sdf, stats["final_decode"] = latent2sdf_hierarchical(x1, bmin, bmax, res, self.vae, device, min_res=final_min_res)
-            elif band:                # a step before the last on the guidance grid
-                sdf = guidance_sdf(x1)
-            else:
-                sdf = latent2sdf(x1, xyz, gsz, self.vae, device, num_chunks)
-            if sparse:                # the final step's mesh from axis tables: no dense point grid on the extractor's side
-                v, f, l, stats["final_extract"] = ops.flexicubes_sparse(ops.grid_axes(bmin, bmax, res), sdf[0].flatten(), res, return_stats=True)
-                return v, f, l
-            return ops.flexicubes(xyz, sdf[0].flatten(), res)
+        hip_dec = getattr(self.vae, "hip_geo", None)
+        decoder = _StepDecoder(self.vae, sch, opts, guid_res, final_res, stats, num_chunks)
 
         # Phases B and C re-extract the object from the latent in every iteration (PL:1391-1393, 1507-1509): vertex count,
         # face count and connectivity change each time.  Fast path: engine.SdfObjective -- iso-surfacing, installing the new
@@ -792,15 +805,39 @@ class GuidedShapePipeline:
             for name in ("params", "adam_m", "adam_v", "adam_t", "flags"):
                 getattr(dst, name).copy_(getattr(src, name))
 
-        def latent_phase(phase, iters, i, t, noise_pred, lr, nan_returns_none):
-            try:
-                return latent_phase_body(phase, iters, i, t, noise_pred, lr, nan_returns_none)
-            finally:          # however the phase ends (a NaN return, an exception), the shared decoder's active-row bound does not outlive it
-                hip_ = getattr(self.vae, "hip_geo", None)
-                if hip_ is not None:
-                    hip_.row_cap = None
+        def phase_ended(phase, i, noise_pred):
+            param_log.append((phase, i, gb.params[0].detach().clone(), noise_pred))
+            if on_phase_end is not None:
+                on_phase_end(phase, i, gb)
 
-        def latent_phase_body(phase, iters, i, t, noise_pred, lr, nan_returns_none):
+        def hand_phase(i):
+            """Phase A with the reference's prints (PL:1351-1355) and, under FOHO_DEBUG_DIR, its plots of the rendered hand normals every 10
+            iterations (PL:1331-1333)."""
+            n = int(cfg0.optimization_steps_hand)
+            cfg_eval, _ = E.phase_cfg("A", cfg0, denoise_i=i, do_update=False)
+            plots = bool(debug_root) and n % 10 == 0
+
+            def first_losses():       # the k = 0 losses the reference prints: one evaluation at the current parameters, no update
+                gb.step(cfg_eval)
+                l0 = gb.loss_dict(0)
+                loss_log.append(("A", i, 0, l0))
+                say(f"Opt step 0, loss_2d_kps: {l0['kps']}, loss_normal_hand: {l0['normal0']}, loss_disp_hand: {l0['disp0']}")
+
+            def plot(rep):            # the render iteration k = 10 rep starts from
+                gb.step(cfg_eval)
+                E.save_grid(E.normal_map(gb, E.L.FACES_HAND), scene["moge_normal"], os.path.join(save_dir, f"rendered_normal_hand_t{i}_opt{10 * rep}.png"))
+
+            flags = _hand_phase(gb, cfg0, i, stats, device, spg=10 if plots else None, after_capture=first_losses,
+                                before_replay=plot if plots else None)
+            # the reference has no NaN guard in phase A (PL:1320-1358): a NaN loss there poisons the hand pose;
+            # here the sticky flag freezes the parameters instead -- say so rather than continue silently
+            if int(flags[0]) & 1:
+                say("Total loss is NaN in the hand-only phase: hand parameters frozen at their last finite value")
+            l = gb.loss_dict(0)
+            say(f"Opt step {n - 1}, loss_2d_kps: {l.get('kps', 0.0)}, total: {l['total']}")
+            phase_ended("A", i, None)
+
+        def latent_phase(phase, iters, i, t, noise_pred, lr, nan_returns_none):
             """Phases B / C (PL:1362-1453 / 1456-1601): `iters` iterations of decode -> fused step -> AdamW."""
             cfg, n_renders = E.phase_cfg(phase, cfg0, denoise_i=i, do_update=True)
             gb.set_n_renders(n_renders)
@@ -813,8 +850,7 @@ class GuidedShapePipeline:
                 cap = tuple(int(x) for x in os.environ["FOHO_OBJ_CAPACITY"].split(","))
             for k in range(int(iters)):
                 opt.zero_grad()
-                x1 = self.scheduler.step_final(noise_pred, t, obj_latents)
-                sdf = guidance_sdf(x1)[0].flatten()
+                sdf = decoder.guidance(self.scheduler.step_final(noise_pred, t, obj_latents))[0]
                 loss, cur = None, gb
                 if use_fast:
                     g2, fobj = fast_objective(cap)
@@ -822,7 +858,7 @@ class GuidedShapePipeline:
                     sync_state(gb, g2)
                     loss = fobj(sdf, cfg)
                     nv, nf, fl = fobj.status()[0]          # one read-back per iteration (the reference's NaN test is one, too)
-                    if getattr(self.vae, "hip_geo", None) is not None:
+                    if hip_dec is not None:
                         _bound_active_rows(self.vae, fobj.active_rows()[0])
                     if fl & 64:                            # empty iso-surface (PL:1394-1397, 1511-1513)
                         print("Invalid mesh detected, aborting step!")
@@ -872,110 +908,55 @@ class GuidedShapePipeline:
                 if cur is not gb:
                     sync_state(cur, gb)
             gb.raise_on_flags(strict_k=False)
-            _check_rows_dropped(getattr(self.vae, "hip_geo", None))
-            param_log.append((phase, i, gb.params[0].detach().clone(), noise_pred.detach().clone()))
-            if on_phase_end is not None:
-                on_phase_end(phase, i, gb)
+            _check_rows_dropped(hip_dec)
+            phase_ended(phase, i, noise_pred.detach().clone())
             return noise_pred.detach().clone()
 
         obj_out = hand_out = None
-        for i, t in enumerate(timesteps_obj):
-            latent_in = torch.cat([obj_latents] * 2) if do_cfg else obj_latents
-            timestep = t.expand(latent_in.shape[0]).to(obj_latents.dtype) / self.scheduler.config.num_train_timesteps
-            noise_pred_obj = self.model(latent_in, timestep, cond_obj, guidance=guidance)
-            if do_cfg:      # trust the learned prior early, the guidance later (PL:1284-1293)
-                scale_i = obj_guidance_scale * (1 - i / n_steps_obj) if i >= guidance_start_step + 1 else obj_guidance_scale
-                c, u = noise_pred_obj.chunk(2)
-                noise_pred_obj = u + scale_i * (c - u)
-
+        for i, t in enumerate(sch.timesteps):
+            noise_pred_obj = self._noise_prediction(sch, obj_latents, i, t, cfg0)
             if i >= handopt_start_step:
                 with torch.enable_grad():
-                    if i == handopt_start_step:                      # phase A: hand only, no latent involved (PL:1296-1358)
+                    if i == handopt_start_step:
                         say(f"Pre-guidance step {i}, optimizing hands only")
-                        cfg, n_renders = E.phase_cfg("A", cfg0, denoise_i=i, do_update=True)
-                        gb.set_n_renders(n_renders)
-                        gb.reset_optimizer()
-                        n = int(cfg0.optimization_steps_hand)
-                        spg = max([d for d in range(1, 51) if n % d == 0]) if n > 0 else 1
-                        if debug_root and n % 10 == 0:
-                            spg = 10        # the reference plots the rendered hand normals every 10 iterations (PL:1331-1333)
-                        graph = gb.capture(cfg, steps_per_graph=spg)
-                        # the k = 0 losses the reference prints (PL:1351-1355): one evaluation at the current parameters, no update
-                        cfg_eval, _ = E.phase_cfg("A", cfg0, denoise_i=i, do_update=False)
-                        gb.step(cfg_eval)
-                        l0 = gb.loss_dict(0)
-                        loss_log.append(("A", i, 0, l0))
-                        say(f"Opt step 0, loss_2d_kps: {l0['kps']}, loss_normal_hand: {l0['normal0']}, loss_disp_hand: {l0['disp0']}")
-                        gb.reset_optimizer()
-                        for rep in range(n // spg):
-                            if debug_root and spg == 10:    # the render iteration k = 10 rep starts from
-                                gb.step(cfg_eval)
-                                E.save_grid(E.normal_map(gb, E.L.FACES_HAND), scene["moge_normal"],
-                                            os.path.join(save_dir, f"rendered_normal_hand_t{i}_opt{10 * rep}.png"))
-                            graph.replay()
-                        stats["inner_iterations"] += n
-                        torch.cuda.synchronize(device)
-                        # the reference has no NaN guard in phase A (PL:1320-1358): a NaN loss there poisons the hand pose;
-                        # here the sticky flag freezes the parameters instead -- say so rather than continue silently
-                        if int(gb.raise_on_flags(strict_k=False)[0]) & 1:
-                            say("Total loss is NaN in the hand-only phase: hand parameters frozen at their last finite value")
-                        l = gb.loss_dict(0)
-                        say(f"Opt step {n - 1}, loss_2d_kps: {l.get('kps', 0.0)}, total: {l['total']}")
-                        param_log.append(("A", i, gb.params[0].detach().clone(), None))
-                        if on_phase_end is not None:
-                            on_phase_end("A", i, gb)
-                    elif i == handopt_start_step + 1:                # phase B: object transform + latent (PL:1361-1453)
-                        say(f"Object optimization step {i}, optimizing object transformation")
-                        noise_pred_obj = latent_phase("B", cfg0.optimization_steps_scale, i, t, noise_pred_obj,
-                                                      cfg0.noise_obj_lr1, nan_returns_none=True)
+                        hand_phase(i)
+                    elif i <= guidance_end_step:
+                        with _latent_phase_scope(hip_dec):
+                            if i == handopt_start_step + 1:              # phase B: object transform + latent (PL:1361-1453)
+                                say(f"Object optimization step {i}, optimizing object transformation")
+                                noise_pred_obj = latent_phase("B", cfg0.optimization_steps_scale, i, t, noise_pred_obj, cfg0.noise_obj_lr1,
+                                                              nan_returns_none=True)
+                            else:                                        # phase C: joint (PL:1455-1601)
+                                say(f"Joint optimization step {i}, optimizing hands and object together")
+                                noise_pred_obj = latent_phase("C", cfg0.optimization_steps_joint, i, t, noise_pred_obj, cfg0.noise_obj_lr2,
+                                                              nan_returns_none=False)
                         if noise_pred_obj is None:
                             return None
-                    elif handopt_start_step + 2 <= i <= guidance_end_step:   # phase C: joint (PL:1455-1601)
-                        say(f"Joint optimization step {i}, optimizing hands and object together")
-                        noise_pred_obj = latent_phase("C", cfg0.optimization_steps_joint, i, t, noise_pred_obj,
-                                                      cfg0.noise_obj_lr2, nan_returns_none=False)
                 noise_pred_obj = noise_pred_obj.detach().clone()
 
             obj_latents = self.scheduler.step(noise_pred_obj, t, obj_latents).prev_sample
 
             # current clean-sample estimate as a mesh in the MoGe world (PL:1612-1661); the last one is the result
-            p = gb.params[0]
-            if i >= handopt_start_step:
-                hand_now = similarity_about_center(hand_moge, p[0], p[4:8], p[1:4])
             last = i == num_inference_steps - 1
-            if last and final_res != octree_res:     # final decode on the fine grid (PL:1626-1642)
-                octree_res = final_res
-                if final_sparse and final_mode == "hierarchical":     # neither the decode nor the extractor reads the dense point grid
-                    xyz_samples, grid_size = None, [octree_res + 1] * 3
-                else:
-                    xyz_np, grid_size, _ = generate_dense_grid_points(bmin, bmax, octree_depth=5, octree_resolution=octree_res,
-                                                                      indexing="ij")
-                    xyz_samples = torch.as_tensor(xyz_np, dtype=torch.float32, device=device)
-            verts, faces, _ = decode_mesh(noise_pred_obj, t, obj_latents, octree_res, xyz_samples, grid_size,
-                                          hierarchical=final_mode == "hierarchical" and last, band=guid_band and not last,
-                                          sparse=final_sparse and last)
-            if verts.shape[0] == 0:
-                print("Invalid mesh detected, aborting step!")
+            res, xyz, extract = decoder.step_grid(last)
+            sdf = decoder.step(self.scheduler.step_final(noise_pred_obj, t, obj_latents), last, res, xyz)
+            obj_now, hand_now = _meshes_in_moge_world(*extract(sdf[0], 0), T_h2m, gb.params[0], hand_moge, hand_faces, i >= handopt_start_step)
+            hand_out = hand_out if hand_now is None else hand_now
+            if obj_now is None:
                 continue
-            obj_world = similarity_about_center(verts @ T_h2m[:3, :3].T + T_h2m[:3, 3], p[8], p[12:16], p[9:12])
-            tex = torch.zeros_like(obj_world)
-            tex[:, 2] = 1.0
-            obj_out = Meshes(verts=[obj_world], faces=[faces], textures=TexturesVertex(verts_features=[tex]))
-            if i >= handopt_start_step:
-                tex_h = torch.zeros_like(hand_now)
-                tex_h[:, 1] = 1.0
-                hand_out = Meshes(verts=[hand_now], faces=[hand_faces], textures=TexturesVertex(verts_features=[tex_h]))
+            obj_out = obj_now
+            obj_world, faces = obj_out.verts_packed(), obj_out.faces_packed()
             if debug_root:      # PL:1664-1667: the scene of this denoising step against the MoGe normals
-                if i >= handopt_start_step:
-                    dv = torch.cat([hand_now, obj_world], 0)
-                    df = torch.cat([hand_faces, faces + hand_now.shape[0]], 0)
+                if hand_now is not None:
+                    dv = torch.cat([hand_now.verts_packed(), obj_world], 0)
+                    df = torch.cat([hand_faces, faces + hand_now.verts_packed().shape[0]], 0)
                 else:
                     dv, df = obj_world, faces
                 dn, _, _ = E.hip_render_fn(device)(dv.detach().cpu().numpy(), df.cpu().numpy(), gb.H, gb.W, scene["fov"])
                 E.save_grid(dn, scene["moge_normal"], os.path.join(save_dir, f"rendered_normal_t{i}.png"))
             if debug_root and i in (14, num_inference_steps - 1):
                 from . import meshio
-                tag = "final" if i == num_inference_steps - 1 else f"guidance_step_{i}"
+                tag = "final" if last else f"guidance_step_{i}"
                 meshio.save_ply(os.path.join(save_dir, f"{tag}_hand_mesh.ply"), hand_out.verts_packed().cpu().numpy(),
                                 hand_faces.cpu().numpy())
                 meshio.save_ply(os.path.join(save_dir, f"{tag}_obj_mesh.ply"), obj_world.cpu().numpy(), faces.cpu().numpy())

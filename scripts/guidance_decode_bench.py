@@ -7,7 +7,7 @@ heads, fp16, random weights) on the HIP geometry decoder.
     (set_kv + decodes), and the forward plus the rows backward (foho_geo_decode_bwd_rows on the full grid) under a FlexiCubes-shaped
     gradient (non-zero on the corners of the torus's sign-changing cubes).  The backward is the same call on both routes.
 (b) pipeline iteration, stand-in networks (noisy random field: the band is wide, closure rounds are many): one inner iteration as
-    pipeline.latent_phase_body runs it -- latent2sdf[_band] -> SdfObjective (FlexiCubes, fused step) -> backward to the noise
+    the pipeline's latent_phase runs it -- latent2sdf[_band] -> SdfObjective (FlexiCubes, fused step) -> backward to the noise
     prediction -- for B = 1, and the call_batch form for B = 4.  Decoded fraction, closure rounds, host reads per iteration.
 
     python scripts/guidance_decode_bench.py [--out profiles/guidance_decode_bench.json] [--iters 5] [--cases a,b] [--min-res 16,32]
@@ -152,7 +152,7 @@ def main():
                     x1 = lat + 0.1 * noise
                     if mode == "dense" and B == 1:
                         sdf = PLN.latent2sdf(x1, xyz, gsz, vae, dev).reshape(1, -1)
-                    elif mode == "dense":      # call_batch's sdf_of: the transformer on all images, the decoder per image
+                    elif mode == "dense":      # the drivers' dense decode (pipeline._StepDecoder): the transformer on all images, the decoder per image
                         tokens = PLN.vae_tokens(vae, 1 / vae.scale_factor * x1)
                         sdf = torch.stack([-hip(q, tokens[b:b + 1]).reshape(-1).float() for b in range(B)], 0)
                     elif B == 1:

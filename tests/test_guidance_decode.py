@@ -273,8 +273,8 @@ def test_pipeline_guidance_decode_switch(tmp_path, monkeypatch):
     res = 24
     kw = dict(config=cfg, renderer=_renderer(sc["fov"]), J_regressor=sc["J_regressor"], guidance_octree_resolution=res, final_octree_resolution=40)
     xyz, gsz = _dense_points(res)
-    checked = {"grad": 0, "nograd": 0, "latent2sdf_band": 0}
-    orig_band, orig_tok = PLN.latent2sdf_band, PLN.sdf_band_from_tokens
+    checked = {"grad": 0, "nograd": 0}
+    orig_tok = PLN.sdf_band_from_tokens
     gen = torch.Generator(device="cuda").manual_seed(7)          # the spies leave the global RNG alone
 
     def check_tokens(tok, sdf):
@@ -296,24 +296,26 @@ def test_pipeline_guidance_decode_switch(tmp_path, monkeypatch):
             hip.row_cap = cap
         checked["grad"] += 1
 
-    def spy_band(pred, xyz_, gsz_, vae, device, bmin, bmax, min_res=None, band=1):
-        """__call__'s route: latent2sdf_band, whose tokens go through sdf_band_from_tokens (checked there)."""
-        n = checked["grad"] + checked["nograd"]
-        sdf, st = orig_band(pred, xyz_, gsz_, vae, device, bmin, bmax, min_res=min_res, band=band)
-        assert st["levels"] == [12, 24] and not st["fallback"] and sdf.shape == (1, res + 1, res + 1, res + 1)
-        assert checked["grad"] + checked["nograd"] == n + 1 and sdf.requires_grad == (torch.is_grad_enabled() and pred.requires_grad)
-        checked["latent2sdf_band"] += 1
-        return sdf, st
-
     def spy_tok(tokens, xyz_, res_, hip_, bmin, bmax, min_res=None, band=1):
-        """Both routes: every image's band field against the dense decode of its tokens."""
+        """Both drivers' route: every image's band field against the dense decode of its tokens."""
         out = orig_tok(tokens, xyz_, res_, hip_, bmin, bmax, min_res=min_res, band=band)
         for t, f in zip(tokens, out[0]):
             check_tokens(t.detach().requires_grad_(t.requires_grad), f)
         return out
 
-    monkeypatch.setattr(PLN, "latent2sdf_band", spy_band)
     monkeypatch.setattr(PLN, "sdf_band_from_tokens", spy_tok)
+
+    # latent2sdf_band itself (the drivers decode at the level of its tokens): its tokens go through sdf_band_from_tokens (checked there)
+    torch.manual_seed(11)
+    for with_grad in (True, False):
+        lat = torch.randn(1, *pipe.vae.latent_shape, device="cuda").requires_grad_(with_grad)
+        n = checked["grad"] + checked["nograd"]
+        with (torch.enable_grad() if with_grad else torch.no_grad()):
+            sdf, st = PLN.latent2sdf_band(lat, xyz, gsz, pipe.vae, "cuda", BMIN, BMAX)
+        assert st["levels"] == [12, 24] and not st["fallback"] and sdf.shape == (1, res + 1, res + 1, res + 1)
+        assert checked["grad"] + checked["nograd"] == n + 1 and sdf.requires_grad == with_grad
+    assert checked == {"grad": 1, "nograd": 1}
+    checked.update(grad=0, nograd=0)
 
     def run(**extra):
         return pipe(image=[img], mc_algo="mc", generator=torch.manual_seed(2), sil_renderer=None, **kw, **paths, **extra)
@@ -323,11 +325,11 @@ def test_pipeline_guidance_decode_switch(tmp_path, monkeypatch):
         assert torch.allclose(h1.verts_packed(), h2.verts_packed(), atol=5e-5)
         assert o1.faces_packed().shape == o2.faces_packed().shape and torch.allclose(o1.verts_packed(), o2.verts_packed(), atol=2e-4)
 
-    none = {"grad": 0, "nograd": 0, "latent2sdf_band": 0}
+    none = {"grad": 0, "nograd": 0}
 
-    def used(n_band):
+    def used():
         # phase B 3 iterations + phase C 2 x 2 with gradient; the per-step decodes of steps 0-3 without
-        assert checked == {"grad": 7, "nograd": 4, "latent2sdf_band": n_band}, checked
+        assert checked == {"grad": 7, "nograd": 4}, checked
         checked.update(none)
 
     base = run()
@@ -336,18 +338,18 @@ def test_pipeline_guidance_decode_switch(tmp_path, monkeypatch):
     st = pipe.stats["guidance_decode"]
     assert st["decodes"] == checked["grad"] + checked["nograd"] and st["levels"] == [12, 24] and st["fallbacks"] == 0
     assert 0 < st["mean_decoded_fraction"] <= st["max_decoded_fraction"] < 1 and st["max_closure_rounds"] >= 0
-    used(11)
+    used()
     same(base, band)
     monkeypatch.setenv("FOHO_GUIDANCE_DECODE", "hierarchical")
     env = run()
-    used(11)
+    used()
     assert pipe.stats["guidance_decode"]["decodes"] == 11
     same(base, env)
     monkeypatch.delenv("FOHO_GUIDANCE_DECODE")
     both = pipe.call_batch([img], [paths], **kw)
     assert "guidance_decode" not in pipe.stats and checked == none
     got = pipe.call_batch([img], [paths], guidance_decode="hierarchical", **kw)
-    used(0)
+    used()
     st = pipe.stats["guidance_decode"]
     assert isinstance(st, list) and len(st) == 1 and st[0]["decodes"] == 11 and st[0]["levels"] == [12, 24]
     same(both[0], got[0])

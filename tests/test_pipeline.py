@@ -83,6 +83,72 @@ def test_similarity_about_center_matches_reference_formula():
     assert torch.allclose(out, (1.3 * (v - c)) @ R.T + c + torch.tensor([0.1, 0.2, -0.3]), atol=1e-5)
 
 
+class _DecoderStandIn:
+    """row_cap, rows_dropped_total and take_rows_dropped as geo_decode.HipGeoDecoder defines them."""
+
+    def __init__(self):
+        self.row_cap = None
+        self.rows_dropped_total = None
+
+    def take_rows_dropped(self):
+        if self.rows_dropped_total is None:
+            return 0
+        n = int(self.rows_dropped_total.item())
+        self.rows_dropped_total.zero_()
+        return n
+
+
+@pytest.mark.parametrize("ending", ["exception", "normal"])
+def test_latent_phase_scope_leaves_nothing_on_the_shared_decoder(ending):
+    """However a latent phase ends, neither its active-row bound nor its dropped-row count outlives it; without a HIP decoder the scope
+    does nothing."""
+    hip = _DecoderStandIn()
+
+    def phase(h):
+        with PLN._latent_phase_scope(h):
+            if h is not None:
+                h.row_cap = 7
+                h.rows_dropped_total = torch.tensor([3], dtype=torch.int32)
+            if ending == "exception":
+                raise KeyError("inside the phase")
+            return "done"
+
+    for h in (hip, None):
+        if ending == "exception":
+            with pytest.raises(KeyError, match="inside the phase"):
+                phase(h)
+        else:
+            assert phase(h) == "done"
+    assert hip.row_cap is None and hip.take_rows_dropped() == 0 and int(hip.rows_dropped_total) == 0
+    # the success path's own check still raises inside the scope, and the scope clears up behind it
+    with pytest.raises(PLN.E.L.FohoError, match="3 active rows exceeded row_cap"):
+        with PLN._latent_phase_scope(hip):
+            hip.row_cap, hip.rows_dropped_total = 7, torch.tensor([3], dtype=torch.int32)
+            PLN._check_rows_dropped(hip)
+    assert hip.row_cap is None and hip.take_rows_dropped() == 0
+
+
+@pytest.mark.parametrize("fn, env, choices", [("final_decode_mode", "FOHO_FINAL_DECODE", ("dense", "hierarchical")),
+                                              ("final_extract_mode", "FOHO_FINAL_EXTRACT", ("dense", "sparse")),
+                                              ("guidance_extract_mode", "FOHO_GUIDANCE_EXTRACT", ("dense", "sparse")),
+                                              ("guidance_decode_mode", "FOHO_GUIDANCE_DECODE", ("dense", "hierarchical"))])
+def test_option_switches_argument_environment_default(monkeypatch, fn, env, choices):
+    mode = getattr(PLN, fn)
+    other = choices[1]
+    for name in ("FOHO_FINAL_DECODE", "FOHO_FINAL_EXTRACT", "FOHO_GUIDANCE_EXTRACT", "FOHO_GUIDANCE_DECODE"):
+        monkeypatch.delenv(name, raising=False)
+    assert mode() == "dense" and mode(None) == "dense" and mode(other) == other
+    monkeypatch.setenv(env, other)
+    assert mode() == other and mode("dense") == "dense"              # the environment wins over the default, the argument over both
+    monkeypatch.setenv(env, "")
+    assert mode() == "dense"
+    for bad_arg, bad_env in (("octree", "dense"), (None, "octree")):
+        monkeypatch.setenv(env, bad_env)
+        with pytest.raises(PLN.E.L.FohoError) as err:
+            mode(bad_arg)
+        assert "'octree'" in str(err.value) and all(c in str(err.value) for c in choices) and fn[:-5] in str(err.value)
+
+
 # ---------------------------------------------------------------------------------------------------------- GPU
 def _scene_for_pipeline(H=128, W=128, radius=0.8):
     """A synthetic image whose object fills the Hunyuan box like a real decode does: the Hunyuan -> MoGe similarity is
@@ -204,6 +270,47 @@ def test_guided_pipeline_end_to_end_on_files(tmp_path, monkeypatch):
     obj0, _ = run(_short_config(noise_lr=0.0))
     v0 = obj0.verts_packed()
     assert v0.shape != ov.shape or not torch.allclose(v0, ov, atol=1e-6)
+
+
+@gpu
+def test_hand_of_the_last_step_is_returned_after_an_empty_final_decode(tmp_path, monkeypatch):
+    """The reference builds a step's hand (PL:1615-1619) before its empty-mesh `continue` (PL:1644-1646) and returns it (PL:1679): when the
+    final decode gives no surface, the result is the object of the last step that had one with the hand of the LAST step -- from
+    `__call__` and from call_batch.  The end-to-end test's configuration; the final grid's extraction (res 40) is made empty."""
+    from PIL import Image
+    from followmyhold_amd import ops
+    sc = _scene_for_pipeline()
+    paths = _write(tmp_path, sc)
+    img = Image.open(paths["cropped_obj_img_path"])
+    pipe = standins.make_standin_pipeline(device="cuda", dtype=torch.float32, seed=1)
+    real, counts = ops.flexicubes, []
+
+    def flexicubes(x, s, res, *a, **kw):
+        out = real(x, s, res, *a, **kw)
+        if res == 40:
+            return tuple(o[:0] for o in out)
+        if not torch.is_grad_enabled() and out[0].shape[0] > 0:
+            counts.append(out[0].shape[0])
+        return out
+
+    monkeypatch.setattr(ops, "flexicubes", flexicubes)
+    kw = dict(config=_short_config(), renderer=_renderer(sc["fov"]), J_regressor=sc["J_regressor"], guidance_octree_resolution=24,
+              final_octree_resolution=40)
+    hand_verts = torch.as_tensor(sc["hand_verts"], device="cuda")
+
+    def check(obj, hand):
+        p = pipe.guidance_batch.params[0]
+        want = PLN.similarity_about_center(hand_verts, p[0], p[4:8], p[1:4])
+        assert torch.allclose(hand.verts_packed(), want, atol=1e-5), float((hand.verts_packed() - want).abs().max())
+        assert obj.verts_packed().shape[0] == counts[-1]          # the last non-empty one, from the guidance grid: step 4 gave nothing
+
+    obj, hand = pipe(image=[img], mc_algo="mc", generator=torch.manual_seed(2), sil_renderer=None, **kw, **paths)
+    # the last phase C moved the hand: a hand kept from the step before would show
+    assert (pipe.param_log[-1][2][:8] - pipe.param_log[-2][2][:8]).abs().max().item() > 1e-6
+    check(obj, hand)
+    counts.clear()
+    (obj, hand), = pipe.call_batch([img], [paths], **kw)
+    check(obj, hand)
 
 
 @gpu
