@@ -15,7 +15,7 @@
 // Grid point (i,j,k) -> (i*G + j)*G + k (generate_dense_grid_points, PL:341-360); cube corners in x-fastest order; cube edges
 // 0-3 along x, 4-7 along y, 8-11 along z (followmyhold_amd/flexi_tables.py).
 // The per-cube arithmetic (index helpers, sign code, dual vertex and l_dev, patch edge count, ring table, quad orientation and split) is
-// flexi_core.h's, shared with the sparse extractor (foho_sflexi.hip) and the weighted one (foho_wflexi.hip).  The five scan kernels
+// flexi_core.h's, shared with the sparse extractor (foho_sflexi.hip) and the weighted one (foho_wflexi.hip).  The four scan kernels
 // are three device functions (scan_load8, scan_block_sum, scan_store8) around their own choice of array and prefix.
 #include "flexi_core.h"
 
@@ -77,7 +77,7 @@ __global__ __launch_bounds__(256) void k_flexi_classify(const float* s, int res,
     }
 }
 
-// ---- exclusive scan of an int32 array (three launches; deterministic).  A workgroup takes FX_ITEMS items, 8 in a row per thread.
+// ---- exclusive scan of an int32 array (two launches: block sums, then every workgroup adds up the sums in front of it; deterministic).  A workgroup takes FX_ITEMS items, 8 in a row per thread.
 // The three pieces of its kernels; s_w = 4 ints of LDS:
 // my 8 items of `in` (0 past n) -> v; their sum
 __device__ __forceinline__ int scan_load8(const int32_t* in, size_t base, size_t n, int* v) {
@@ -120,39 +120,8 @@ __global__ __launch_bounds__(256) void k_scan_sums(const int32_t* in, size_t n, 
     const int sum = scan_block_sum(in, (size_t)blockIdx.x * FX_ITEMS + (size_t)threadIdx.x * 8, n, s_w);
     if (threadIdx.x == 0) bsum[blockIdx.x] = sum;
 }
-__global__ __launch_bounds__(256) void k_scan_bsums(int32_t* bsum, int nb, int32_t* total) {
-    // one workgroup: exclusive scan of the block sums in place, total appended at bsum[nb] and stored to *total
-    __shared__ int s_w[4];
-    __shared__ int s_carry;
-    if (threadIdx.x == 0) s_carry = 0;
-    __syncthreads();
-    for (int base = 0; base < nb; base += 256) {
-        const int i = base + threadIdx.x;
-        const int v = (i < nb) ? bsum[i] : 0;
-        const unsigned incl = wave_incl_scan((unsigned)v);
-        if (lane_id() == 63) s_w[wave_id()] = (int)incl;
-        __syncthreads();
-        int off = s_carry;
-        for (int w = 0; w < wave_id(); w++) off += s_w[w];
-        if (i < nb) bsum[i] = off + (int)incl - v;
-        __syncthreads();
-        if (threadIdx.x == 0) s_carry += (s_w[0] + s_w[1]) + (s_w[2] + s_w[3]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        bsum[nb] = s_carry;
-        *total = s_carry;
-    }
-}
-__global__ __launch_bounds__(256) void k_scan_apply(const int32_t* in, size_t n, const int32_t* bsum, int32_t* out) {
-    __shared__ int s_w[4];
-    const size_t base = (size_t)blockIdx.x * FX_ITEMS + (size_t)threadIdx.x * 8;
-    int v[8];
-    const int sum = scan_load8(in, base, n, v);
-    scan_store8(v, sum, bsum[blockIdx.x], base, n, out, s_w);  // bsum: scanned by k_scan_bsums
-}
 
-// the two scans of the extraction (dual vertices per cube, quads per grid edge) ride in the same three launches
+// the two scans of the extraction (dual vertices per cube, quads per grid edge) ride in the same two launches
 struct Scan2 {
     const int32_t* in[2];
     size_t n[2];
@@ -203,7 +172,7 @@ __global__ __launch_bounds__(256) void k_scan2_apply(Scan2 a, int32_t* counts) {
         }
     }
 }
-// single array, same scheme (topology tables of capacity mode)
+// single array, same scheme (both topology-table builders: k_topo.inc's topo_scan)
 __global__ __launch_bounds__(256) void k_scan_apply_p(const int32_t* in, size_t n, const int32_t* bsum, int32_t* out) {
     __shared__ int s_w[4];
     const size_t base = (size_t)blockIdx.x * FX_ITEMS + (size_t)threadIdx.x * 8;

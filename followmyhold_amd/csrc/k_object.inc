@@ -11,11 +11,12 @@
 //   k_object_adopt    per image: counts -> image record (Vo, Fo, n_edges = 3 Fo / 2; capacity overflow -> empty object +
 //                     flag bit 4; odd face count -> empty object + flag bit 5), int64 local face ids -> int32 global ids behind the hand's faces, valence histogram of
 //                     all valid (face, corner) pairs, clears the AABB keys
-//   scan (2 launches) valences -> list offsets (k_flexi.inc)
-//   k_object_fill     per (face, corner): append to the vertex's list (atomic cursor; order fixed by the next kernel);
+//   topo_scan         valences -> list offsets (k_topo.inc; 2 launches)
+//   k_object_fill     per (face, corner): append to the vertex's TEMPORARY list (atomic cursor; order fixed by the next kernel);
 //                     extra workgroups: AABB of the new input meshes (centre of the similarity transform, PL:111)
-//   k_topo_finish_b   per vertex: sort its list by (corner, face), neighbour list + manifold check (flag bit 5), the
-//                     (vertex, face) pairs of the normal backward (k_pair_table); hands the counters back zeroed
+//   k_topo_finish_b   per vertex: k_topo.inc's topo_vertex -- the core it shares with the exact-size k_topo_finish -- writing the
+//                     ordered list, the neighbour list and the (vertex, face) pairs of the normal backward (what k_pair_table
+//                     writes on the exact-size path); manifold check -> flag bit 5 of the owning image; hands the counters back zeroed
 
 __global__ __launch_bounds__(256) void k_object_adopt(Ctx c, foho_image* img_rw, int32_t* faces_rw, const int32_t* counts,
                                                       const int64_t* obj_faces, int verts_cap, int faces_cap, int32_t* cnt) {
@@ -60,136 +61,31 @@ __global__ __launch_bounds__(256) void k_object_fill(Ctx c, BboxCfg bc, int fgri
     inc_tmp[inc_off[v] + atomicAdd(&cursor[v], 1)] = (face << 2) | corner;
 }
 
-// per vertex (all Vtot capacity slots; slots past an image's actual count have empty lists).  64 threads per workgroup.
-// Valences up to TOPO_FAST: registers + ranking by counting.  Longer lists (up to TOPO_MAXVAL): private lists in LDS
-// (stride 49 words: conflict free; run-time indexed private arrays would live in scratch memory) + insertion sort.
-constexpr int TOPO_LDS_STRIDE = TOPO_MAXVAL + 1;
-constexpr int TOPO_FAST = 16;
-__global__ __launch_bounds__(64) void k_topo_finish_b(const int32_t* faces, int Vtot, int Fkey, const uint8_t* obj_flag,
-                                                      const int32_t* inc_off, const int32_t* inc_tmp, int32_t* inc_fc,
-                                                      int32_t* nbr_idx, unsigned long long* pair_v, const foho_image* img, int B, int32_t* flags,
-                                                      int32_t* cnt, int32_t* cursor) {
-    __shared__ int s_e[64 * TOPO_LDS_STRIDE], s_d[64 * TOPO_LDS_STRIDE], s_p[64 * TOPO_LDS_STRIDE];
-    const int v = blockIdx.x * 64 + threadIdx.x;
+// per vertex (all Vtot capacity slots; slots past an image's actual count have empty lists): topo_vertex (k_topo.inc) from the
+// temporary list into the tables, with the pair table.  Hand vertices get neighbour lists too but only object vertices are checked.
+// A vertex that fails (flag bit 5 of the image that owns it) with more than TOPO_MAXVAL faces has nothing written.
+__global__ __launch_bounds__(TOPO_TPB) void k_topo_finish_b(const int32_t* faces, int Vtot, int Fkey, const uint8_t* obj_flag,
+                                                            const int32_t* inc_off, const int32_t* inc_tmp, int32_t* inc_fc,
+                                                            int32_t* nbr_idx, unsigned long long* pair_v, const foho_image* img, int B,
+                                                            int32_t* flags, int32_t* cnt, int32_t* cursor) {
+    __shared__ int s_e[TOPO_LDS_LIST], s_d[TOPO_LDS_LIST], s_p[TOPO_LDS_LIST];
+    const int v = blockIdx.x * TOPO_TPB + threadIdx.x, t = threadIdx.x * TOPO_LDS_STRIDE;
     if (v >= Vtot) return;
     const int e0 = inc_off[v], n = inc_off[v + 1] - e0;
-    cnt[v] = 0;      // counters go back clean for the next iteration
+    cnt[v] = 0;  // counters go back clean for the next iteration
     cursor[v] = 0;
     if (n <= 0) return;
-    int bad = 0;
-    if (n > TOPO_MAXVAL) {
-        bad = 1;
-    } else if (n <= TOPO_FAST) {
-        // Up to 16 incident faces (every vertex of a dual-marching-cubes surface, nearly every MANO vertex): the list stays
-        // in registers and is ordered by COUNTING -- rank = number of smaller keys, all compile-time indexed, no dependent
-        // chain -- instead of by insertion (a chain of dependent LDS round trips per move: 30 us for this kernel).
-        int x[TOPO_FAST], f[TOPO_FAST][3];
-#pragma unroll
-        for (int u = 0; u < TOPO_FAST; u++) x[u] = inc_tmp[e0 + min(u, n - 1)];
-#pragma unroll
-        for (int u = 0; u < TOPO_FAST; u++)
-            for (int k = 0; k < 3; k++) f[u][k] = faces[3 * (size_t)(x[u] >> 2) + k];
-        unsigned key[TOPO_FAST];
-        int d[TOPO_FAST], pv[TOPO_FAST];
-#pragma unroll
-        for (int u = 0; u < TOPO_FAST; u++) {
-            const int corner = x[u] & 3;
-            key[u] = (u < n) ? (((unsigned)corner << 28) | (unsigned)(x[u] >> 2)) : 0xffffffffu;  // (corner, face): unique
-            d[u] = (u < n) ? ((corner == 0) ? f[u][1] : ((corner == 1) ? f[u][2] : f[u][0])) : 0x7fffffff;
-            pv[u] = (corner == 0) ? f[u][2] : ((corner == 1) ? f[u][0] : f[u][1]);
-        }
-        const bool check = obj_flag[v] != 0;
-#pragma unroll
-        for (int u = 0; u < TOPO_FAST; u++) {
-            int rk = 0, rd = 0, dup = 0, found = 0;
-#pragma unroll
-            for (int j = 0; j < TOPO_FAST; j++) {
-                rk += (key[j] < key[u]) ? 1 : 0;
-                rd += (d[j] < d[u] || (d[j] == d[u] && j < u)) ? 1 : 0;
-                dup |= (j < u && d[j] == d[u]) ? 1 : 0;     // more than two faces on an edge
-                found |= (d[j] == pv[u]) ? 1 : 0;            // closed: the previous vertex is a neighbour too
-            }
-            if (u < n) {
-                inc_fc[e0 + rk] = x[u];
-                pair_v[e0 + rk] = pack_pair(f[u][0], f[u][1], f[u][2], x[u] & 3);
-                nbr_idx[e0 + rd] = d[u];
-                if (check) bad |= dup | (found ^ 1);
-            }
-        }
-    } else {
-        int* e = s_e + threadIdx.x * TOPO_LDS_STRIDE;
-        int* d = s_d + threadIdx.x * TOPO_LDS_STRIDE;
-        int* pv = s_p + threadIdx.x * TOPO_LDS_STRIDE;
-        // the list, eight loads in flight at a time (valences are 4-8 for a dual-marching-cubes surface)
-        for (int base = 0; base < n; base += 8) {
-            int x[8];
-#pragma unroll
-            for (int u = 0; u < 8; u++) x[u] = inc_tmp[e0 + min(base + u, n - 1)];
-#pragma unroll
-            for (int u = 0; u < 8; u++)
-                if (base + u < n) e[base + u] = x[u];
-        }
-        for (int a = 1; a < n; a++) {  // insertion sort by (corner, face), in LDS
-            const int x = e[a];
-            const long long kx = (long long)(x & 3) * Fkey + (x >> 2);
-            int b2 = a - 1;
-            while (b2 >= 0) {
-                const int y = e[b2];
-                if (((long long)(y & 3) * Fkey + (y >> 2)) <= kx) break;
-                e[b2 + 1] = y;
-                b2--;
-            }
-            e[b2 + 1] = x;
-        }
-        // the faces of the list, 24 loads in flight at a time: pair table, next vertex (neighbour), previous vertex
-        for (int base = 0; base < n; base += 8) {
-            int x[8], f[8][3];
-#pragma unroll
-            for (int u = 0; u < 8; u++) x[u] = e[min(base + u, n - 1)];
-#pragma unroll
-            for (int u = 0; u < 8; u++)
-                for (int k = 0; k < 3; k++) f[u][k] = faces[3 * (size_t)(x[u] >> 2) + k];
-#pragma unroll
-            for (int u = 0; u < 8; u++) {
-                if (base + u >= n) break;
-                const int corner = x[u] & 3;
-                inc_fc[e0 + base + u] = x[u];
-                pair_v[e0 + base + u] = pack_pair(f[u][0], f[u][1], f[u][2], corner);
-                d[base + u] = (corner == 0) ? f[u][1] : ((corner == 1) ? f[u][2] : f[u][0]);
-                pv[base + u] = (corner == 0) ? f[u][2] : ((corner == 1) ? f[u][0] : f[u][1]);
-            }
-        }
-        for (int a = 1; a < n; a++) {  // neighbours ascending
-            const int x = d[a];
-            int b2 = a - 1;
-            while (b2 >= 0) {
-                const int y = d[b2];
-                if (y <= x) break;
-                d[b2 + 1] = y;
-                b2--;
-            }
-            d[b2 + 1] = x;
-        }
-        for (int q = 0; q < n; q++) nbr_idx[e0 + q] = d[q];
-        if (obj_flag[v]) {  // the edge loss runs over object vertices: only they must be closed and manifold
-            for (int q = 1; q < n; q++) bad |= (d[q] == d[q - 1]);  // a duplicate: more than two faces on an edge
-            for (int q = 0; q < n && !bad; q++) {                   // closed: every previous vertex is a neighbour too
-                const int p = pv[q];
-                bool found = false;
-                for (int r = 0; r < n; r++) found = found || (d[r] == p);
-                bad = !found;
-            }
-        }
-    }
-    if (bad)
+    const int st = topo_vertex<true, true>(faces, inc_tmp, e0, n, Fkey, obj_flag[v] != 0, inc_fc, nbr_idx, pair_v, s_e + t, s_d + t, s_p + t);
+    if (st)
         for (int b = 0; b < B; b++)
             if (v >= img[b].v_off && v < img[b].v_off + img[b].Vh + img[b].Vo) atomicOr(&flags[b], 32);
 }
 
+// counters over Vtot + 1 items (the scan of the extra zero is the closing offset); the tail is the temporary incidence list
+static TopoWs carve_object(void* ws, int32_t Vtot, int32_t Ftot) { return carve_topo(ws, (size_t)Vtot + 1, (size_t)Ftot * 3 * 4); }
+
 extern "C" size_t foho_object_workspace_bytes(int32_t Vtot, int32_t Ftot) {
-    if (Vtot < 1 || Ftot < 1) return 0;
-    const size_t n = (size_t)Vtot + 1, nb = (n + FX_ITEMS - 1) / FX_ITEMS;
-    return 2 * al(n * 4) + al((nb + 1) * 4) + al((size_t)Ftot * 3 * 4);
+    return (Vtot < 1 || Ftot < 1) ? 0 : carve_object(nullptr, Vtot, Ftot).total;
 }
 
 // The workspace must be zero-filled before its FIRST use; the kernels hand the counters back zeroed.
@@ -217,29 +113,21 @@ extern "C" int foho_object_update(const foho_step_desc* desc, const int32_t* cou
     }
     hipStream_t stream = (hipStream_t)stream_;
     Ctx c = make_ctx(*desc, w);
-    const size_t n = (size_t)d.Vtot + 1;
-    const int nb = (int)((n + FX_ITEMS - 1) / FX_ITEMS);
-    char* p = (char*)workspace;
-    int32_t* cnt = (int32_t*)p;
-    int32_t* cursor = (int32_t*)(p + al(n * 4));
-    int32_t* bsum = (int32_t*)(p + 2 * al(n * 4));
-    int32_t* inc_tmp = (int32_t*)(p + 2 * al(n * 4) + al(((size_t)nb + 1) * 4));
+    const TopoWs t = carve_object(workspace, d.Vtot, d.Ftot);
+    int32_t* inc_tmp = (int32_t*)t.tail;
     const int fgrid = cdiv(3 * d.Fmax, 256);
     hipLaunchKernelGGL(k_object_adopt, dim3(std::max(1, std::min(fgrid, 128)), d.B), dim3(256), 0, stream, c,
-                       const_cast<foho_image*>(desc->images), const_cast<int32_t*>(desc->faces), counts, obj_faces, d.Vo_max, faces_cap, cnt);
+                       const_cast<foho_image*>(desc->images), const_cast<int32_t*>(desc->faces), counts, obj_faces, d.Vo_max, faces_cap, t.cnt);
     CHECK_LAUNCH("k_object_adopt");
-    hipLaunchKernelGGL(k_scan_sums, dim3(nb), dim3(256), 0, stream, cnt, n, bsum);
-    CHECK_LAUNCH("k_scan_sums");
-    hipLaunchKernelGGL(k_scan_apply_p, dim3(nb), dim3(256), 0, stream, cnt, n, bsum, const_cast<int32_t*>(desc->inc_off));
-    CHECK_LAUNCH("k_scan_apply_p");
+    if (const int rc = topo_scan(t, (size_t)d.Vtot + 1, const_cast<int32_t*>(desc->inc_off), stream)) return rc;
     BboxCfg bc;
     bc.nbh = cdiv(d.Vh_max > 0 ? d.Vh_max : 1, 256);
     bc.nbo = cdiv(d.Vo_max > 0 ? d.Vo_max : 1, 256);
-    hipLaunchKernelGGL(k_object_fill, dim3(fgrid + bc.nbh + bc.nbo, d.B), dim3(256), 0, stream, c, bc, fgrid, desc->inc_off, cursor, inc_tmp);
+    hipLaunchKernelGGL(k_object_fill, dim3(fgrid + bc.nbh + bc.nbo, d.B), dim3(256), 0, stream, c, bc, fgrid, desc->inc_off, t.cursor, inc_tmp);
     CHECK_LAUNCH("k_object_fill");
-    hipLaunchKernelGGL(k_topo_finish_b, dim3(cdiv(d.Vtot, 64)), dim3(64), 0, stream, desc->faces, d.Vtot, d.Ftot, obj_flag, desc->inc_off,
+    hipLaunchKernelGGL(k_topo_finish_b, dim3(cdiv(d.Vtot, TOPO_TPB)), dim3(TOPO_TPB), 0, stream, desc->faces, d.Vtot, d.Ftot, obj_flag, desc->inc_off,
                        inc_tmp, const_cast<int32_t*>(desc->inc_fc), const_cast<int32_t*>(desc->nbr_idx), c.pair_v, desc->images, d.B,
-                       desc->flags, cnt, cursor);
+                       desc->flags, t.cnt, t.cursor);
     CHECK_LAUNCH("k_topo_finish_b");
     return FOHO_OK;
 }

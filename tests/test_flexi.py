@@ -421,3 +421,144 @@ def test_capacity_mode_flags_overflow_and_open_surfaces():
     gb.flags.zero_()
     o.run(s0.cuda(), cfg)                                    # the next closed surface is served again
     assert o.status()[0][2] == 0
+
+
+# ---- the per-vertex topology core (k_topo.inc's topo_vertex) where its two callers used to differ: valences above 16.
+# No other mesh of the suite has a vertex with more than 11 incident faces.
+def _bipyramid(n):
+    """n-gon bipyramid: n + 2 vertices, faces (i, i+1, top) and (i+1, i, bottom) -- closed, consistently oriented, both
+    apexes of valence n, every rim vertex of valence 4."""
+    a = 2 * np.pi * np.arange(n) / n
+    v = np.concatenate([np.stack([np.cos(a), np.sin(a), 0 * a], 1), [[0, 0, 1.0], [0, 0, -1.0]]]).astype(np.float32)
+    i = np.arange(n)
+    j = (i + 1) % n
+    f = np.concatenate([np.stack([i, j, np.full(n, n)], 1), np.stack([j, i, np.full(n, n + 1)], 1)]).astype(np.int64)
+    return v * 0.05, f
+
+
+def _ico2_scene():
+    from helpers import make_scene
+    return {k: (v.numpy() if isinstance(v, torch.Tensor) else v) for k, v in make_scene("ico2", 64, 64, seed=0).items()}
+
+
+def _assert_host_tables(gb, f, what):
+    """inc_off / inc_fc of the whole packed mesh and the neighbour lists of the object's vertices against the numpy builders."""
+    from followmyhold_amd import engine as E
+    Vh, Fh, Vtot = gb.meta[0]["Vh"], gb.meta[0]["Fh"], gb.Vtot
+    faces = np.concatenate([gb.faces[:Fh].cpu().numpy().astype(np.int64), f + Vh])
+    inc_off, inc_fc = E.incidence_csr(faces, Vtot)
+    n_inc = int(inc_off[-1])
+    assert np.array_equal(gb.inc_off.cpu().numpy(), inc_off), what
+    assert np.array_equal(gb.inc_fc.cpu().numpy()[:n_inc], inc_fc), what
+    off, idx = E.neighbour_csr(E.unique_edges(f) + Vh, Vtot)
+    d_off, d_idx = gb.nbr_off.cpu().numpy(), gb.nbr_idx.cpu().numpy()
+    for vv in range(Vh, Vh + int(f.max()) + 1):
+        assert np.array_equal(d_idx[d_off[vv]:d_off[vv + 1]], idx[off[vv]:off[vv + 1]]), (what, vv)
+
+
+def _install(gb, v, f):
+    """Capacity mode: the mesh into image 0's object slots, as foho_flexi_fwd would leave it, then foho_object_update."""
+    lo, _ = gb.obj_slot(0)
+    gb.verts_in[lo:lo + len(v)] = torch.from_numpy(v).to(gb.device)
+    gb.obj_faces64[0, :len(f)] = torch.from_numpy(f).to(gb.device)
+    gb.obj_counts[0] = torch.tensor([len(v), len(f), 0], dtype=torch.int32)
+    gb.adopt_objects()
+    torch.cuda.synchronize()
+
+
+def test_bipyramid_is_a_closed_manifold_of_valence_n():
+    from followmyhold_amd import engine as E
+    for n in (16, 17, 20, 48, 49):
+        v, f = _bipyramid(n)
+        assert len(v) == n + 2 and len(E.unique_edges(f)) == 3 * len(f) // 2 == 3 * n
+        assert np.bincount(f.reshape(-1)).tolist() == [4] * n + [n, n]
+        assert _topology(v.astype(np.float64), f)[2] > 0          # outward
+
+
+@gpu
+@pytest.mark.parametrize("n", [16, 17, 48, 49])
+def test_exact_size_tables_at_the_register_and_lds_path_limits(n):
+    """update_object -> foho_topology_tables with apex valence 16 (the last list kept in registers), 17 and 48 (the LDS lists,
+    shortest and longest), 49 (overflow exit: flag bit 0, the sort path serves the mesh)."""
+    from followmyhold_amd import engine as E
+    gb = E.GuidanceBatch([_ico2_scene()], grid_res=16)
+    v, f = _bipyramid(n)
+    gb.update_object(v, f)
+    _assert_host_tables(gb, f, n)
+    assert gb.meta[0]["n_edges"] == 3 * n
+    assert (gb.nbr_off.data_ptr() == gb.inc_off.data_ptr()) == (n <= 48)     # device path taken / refused
+
+
+@gpu
+def test_capacity_mode_tables_at_the_register_and_lds_path_limits():
+    """The same meshes through adopt_objects (foho_object_update); valence 49 raises bit 5, and the next mesh finds the
+    counters clean."""
+    from followmyhold_amd import engine as E
+    gb = E.GuidanceBatch([_ico2_scene()], grid_res=16, obj_capacity=(64, 128))
+    for n in (16, 17, 48, 49, 17):
+        v, f = _bipyramid(n)
+        gb.flags.zero_()
+        _install(gb, v, f)
+        flags = int(gb.flags[0])
+        if n == 49:
+            assert flags & 32
+        else:
+            assert flags == 0, n
+            _assert_host_tables(gb, f, n)
+
+
+@gpu
+def test_capacity_mode_pair_table_of_a_long_list_serves_the_step():
+    """Valence 17: the pair table written from the LDS lists (capacity mode) against k_pair_table's (exact-size batch) by what
+    the step makes of them -- the tolerances of test_capacity_mode_objective_matches_the_oracle_chain_and_the_exact_size_path."""
+    from followmyhold_amd import engine as E
+    sc = _ico2_scene()
+    v, f = _bipyramid(17)
+    cfg, _ = E.phase_cfg("C", denoise_i=19, do_update=False)
+    cap = E.GuidanceBatch([sc], grid_res=16, obj_capacity=(64, 128))
+    _install(cap, v, f)
+    assert int(cap.flags[0]) == 0
+    cap.step(cfg)
+    exact = E.GuidanceBatch([dict(sc, obj_verts=v, obj_faces=f)], grid_res=16)
+    assert exact.nbr_off.data_ptr() == exact.inc_off.data_ptr()                # built by foho_topology_tables
+    exact.step(cfg)
+    torch.cuda.synchronize()
+    assert np.allclose(cap.losses.cpu().numpy(), exact.losses.cpu().numpy(), rtol=1e-6, atol=1e-9)
+    lo, _ = cap.obj_slot(0)
+    g, ge = cap.grad_verts_in[lo:lo + len(v)].cpu().numpy(), exact.grad_obj_verts(0).cpu().numpy()
+    assert np.linalg.norm(ge) > 0 and np.linalg.norm(g - ge) <= 1e-4 * np.linalg.norm(ge)
+
+
+@gpu
+@pytest.mark.parametrize("case,bad", [("closed", False), ("open_fan", True), ("reversed_face", True)])
+def test_manifold_check_on_the_lds_path(case, bad):
+    """Valence 20 with only the top apex checked, so that only the LDS path can raise the flag: the closed bipyramid passes; an
+    open fan (the two faces on rim edge (0, 1) removed) and a reversed top face (a duplicate neighbour, a missing previous
+    vertex) do not.  Exact size: bit 1 of foho_topology_tables' flag; capacity mode: bit 5 of the image's flags."""
+    from followmyhold_amd import engine as E
+    L = E.L
+    n = 20
+    v, f = _bipyramid(n)
+    if case == "open_fan":
+        f = np.delete(f, [0, n], 0)
+        assert len(f) == 38
+    elif case == "reversed_face":
+        f[0] = [1, 0, n]
+    gb = E.GuidanceBatch([_ico2_scene()], grid_res=16, obj_capacity=(64, 128))
+    Vh, Fh, Vtot = gb.meta[0]["Vh"], gb.meta[0]["Fh"], gb.Vtot
+    only_apex = torch.zeros(Vtot, dtype=torch.uint8, device=gb.device)
+    only_apex[Vh + n] = 1
+    # exact size, straight through the C ABI
+    faces = torch.cat([gb.faces[:Fh], torch.from_numpy(f + Vh).to(torch.int32).to(gb.device)]).contiguous()
+    V, F = Vh + n + 2, len(faces)
+    nws = gb.lib.foho_topology_workspace_bytes(V)
+    ws = torch.empty(nws, dtype=torch.uint8, device=gb.device)
+    inc_off, inc_fc, nbr = (torch.zeros(k, dtype=torch.int32, device=gb.device) for k in (V + 1, 3 * F, 3 * F))
+    flag = torch.zeros(1, dtype=torch.int32, device=gb.device)
+    L.check(gb.lib.foho_topology_tables(L._p(faces), V, F, L._p(only_apex), L._p(inc_off), L._p(inc_fc), L._p(nbr), L._p(flag), L._p(ws), nws,
+                                        L._stream(gb.device)), "foho_topology_tables")
+    assert int(flag.item()) == (2 if bad else 0)
+    # capacity mode
+    gb.obj_flag = only_apex
+    _install(gb, v, f)
+    assert int(gb.flags[0]) == (32 if bad else 0)
