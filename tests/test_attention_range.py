@@ -182,7 +182,9 @@ def _assert_lse(tag, nlse, lse_nat, op, M):
     assert np.isneginf(nlse[:, M:]).all(), f"{tag}: the pad rows of nlse must be -inf"       # (P = 0 for them in the backward)
 
 
-def _assert_grads(tag, grads, op, O16):
+def _grad_refs_and_bounds(op, O16):
+    """-> {name: (g_ref, B_g, floor, U)} for dV, dQ, dK: the referee's gradients and the three terms of `_assert_grads`' tolerance
+    8 eps B_g + floor + U (tests/test_vae_stages.py carries the same tolerance through the qk_norm backward)."""
     dQ, dK, dV, _ = R.backward(op["Qs"], op["K"], op["V"], op["dO"], O16)
     B = R.bounds(op["Qs"], op["K"], op["V"], op["dO"], O16)
     # fp16 UNDERFLOW, the rounding the relative bound below does not contain: below 2^-14 fp16 is subnormal, its rounding error is half a
@@ -194,12 +196,15 @@ def _assert_grads(tag, grads, op, O16):
     a64 = lambda n: np.abs(op[n].astype(np.float64))
     U = {"dV": 2.0 ** -25 * (a64("dO").sum(axis=1, keepdims=True) + 1.0), "dK": 2.0 ** -25 * (R.LN2 * a64("Qs").sum(axis=1, keepdims=True) + 1.0),
          "dQ": 2.0 ** -25 * (a64("K").sum(axis=1, keepdims=True) / 8.0 + 1.0)}
+    return {name: (ref, B[name], 2.0 ** -24 * np.abs(ref).max(), U[name]) for name, ref in (("dV", dV), ("dQ", dQ), ("dK", dK))}
+
+
+def _assert_grads(tag, grads, op, O16):
     worst, raw = {}, {}
-    for name, ref in (("dV", dV), ("dQ", dQ), ("dK", dK)):
+    for name, (ref, B, floor, U) in _grad_refs_and_bounds(op, O16).items():
         got = grads[name].astype(np.float64)
         assert np.isfinite(got).all(), f"{tag}: {name} is not finite ({np.isnan(got).sum()} NaN of {got.size})"
-        floor = 2.0 ** -24 * np.abs(ref).max()
-        worst[name], raw[name] = _ratio(np.abs(got - ref), B[name], floor + U[name]), _ratio(np.abs(got - ref), B[name], floor)
+        worst[name], raw[name] = _ratio(np.abs(got - ref), B, floor + U), _ratio(np.abs(got - ref), B, floor)
     print(f"{tag}: " + "  ".join(f"{k} err / (eps B) {v:.3f} (raw {raw[k]:.3f})" for k, v in worst.items()))
     # |g - g_ref| <= 8 eps B_g + 2^-24 max |g_ref| (+ the underflow term above).  Five fp16 roundings lie between the operands and a stored
     # gradient: P (operand of dV = P^T dO), dS (operand of dQ and dK), O inside delta = rowsum(dO O) (the referee is GIVEN the stored O;

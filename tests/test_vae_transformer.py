@@ -1,7 +1,8 @@
 """The ShapeVAE transformer of latent2sdf on the matrix cores (foho_vae_fwd / foho_vae_bwd, csrc/foho_vae.inc) against the torch module of
 the same shape in float32 on the same fp16-representable weights (PL:295 `pred = vae(pred)`; PL:1391-1393, 1507-1509: its backward to the
 latent): one layer and a stack, both module layouts (the stand-in's q / kv pair, hy3dgen's interleaved c_qkv with qk_norm), one image and
-a batch, forward tokens and the gradient of the input.  fp16 storage / fp32 accumulation: tolerances of tests/test_geo_decode.py."""
+a batch, forward tokens and the gradient of the input.  fp16 storage / fp32 accumulation: tolerances of tests/test_geo_decode.py.
+Where these tolerances are justified: tests/test_vae_stages.py (every launch against a float64 referee on its stored operands, derived bounds)."""
 import ctypes
 
 import pytest
