@@ -1,5 +1,6 @@
 // foho_vae.inc -- the ShapeVAE transformer of `latent2sdf` (PL:295 `pred = vae(pred)`), forward and backward to its input tokens, on the
-// kernels of foho_geo.hip (included at its end: same translation unit, same GEMM / attention templates).
+// kernels of foho_geo.hip (included at its end, behind geo_host.inc: same translation unit, same GEMM / attention templates, driven through
+// geo_host.inc's launchers -- gemm() with an Epi, attn_fwd / attn_bwd / attn_dq / attn_bwd_split with their operand structs).
 //
 // Reference: third_party_patches/hy3dgen/shapegen/pipelines.py:292-296 (latent2sdf), 1391-1393 / 1507-1509 (the decode under autograd in
 // every inner iteration of phases B and C), 1600 (loss.backward()).  hy3dgen's ShapeVAE.forward is post_kl -> Transformer: sixteen
@@ -180,24 +181,17 @@ static VaeSaved vae_saved(const foho_vae_desc* d) {
     return l;
 }
 
-}  // namespace geo
-
-// The attention backward of one image inside the chain (the split form: FOHO_VAE_SPLIT_DKV, or too few (head, key block) workgroups to
-// fill the chip): like sdpa_bwd_image, with every streamed operand already there -- Qs, Qs^T, K^T from the forward's projection epilogue
-// (EP_PACK), dO^T and delta from the epilogue of the GEMM that produced dO (EP_TRANS | EP_DELTA).
-static int vae_attn_bwd_image(const SdpaLayout& l, char* base, const h16* qkv, int ld3, const h16* dO, const float* nls, h16* dqkv, const h16* qs, const h16* qst,
-                              const h16* dot, int ldt, const h16* kt, const float* delta, int Lt, int heads, hipStream_t s) {
-    const int W = heads * 64, nkb = Lt / 128;
-    float* part = (float*)(base + l.part);
-    const h16 *kb = qkv + W, *vb = qkv + 2 * W;
-    const int splits = l.splits;
-    hipLaunchKernelGGL(k_geo_attn_bwd, dim3(8 * ((heads * splits + 7) / 8) * nkb), dim3(256), 0, s, qs, qst, dO, dot, ldt, nls, delta, kb, ld3, W, heads, Lt, splits, Lt, 0, part,
-                       (const int*)nullptr, vb, 64, (h16*)nullptr, (h16*)nullptr, ld3);
-    const size_t n4 = (size_t)Lt * 2 * W / 4;
-    hipLaunchKernelGGL(k_geo_dkv_reduce16, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, part, splits, Lt, W, dqkv + W, dqkv + 2 * W, ld3);
-    hipLaunchKernelGGL(k_geo_attn_dq, dim3(((Lt + DQQ - 1) / DQQ) * heads), dim3(256), 0, s, qs, dO, W, kb, ld3, W, kt, Lt, nls, delta, dqkv, Lt, heads, vb, 64, ld3);
-    return launch_ok("vae attention backward (split)") ? FOHO_OK : FOHO_ERR_LAUNCH;
+// (rstd, rstd mean) of the rows of X (M, width): one wave per row
+static void vae_rowstat(hipStream_t s, const h16* X, int M, int width, float eps, float2* rowstat) {
+    hipLaunchKernelGGL(k_vae_rowstat, dim3((M + 3) / 4), dim3(256), 0, s, X, M, width, eps, rowstat);
 }
+// qk_norm's backward in place on dQKV (M, 3 heads x 64), 8 lanes per (row, q | k, head).  PRE: the un-normalised projection; norm: q_norm's 132 floats, then k_norm's
+static void vae_qknorm_bwd(hipStream_t s, h16* dQKV, const h16* PRE, int M, int heads, const float* norm) {
+    const size_t lanes = (size_t)M * 2 * heads * 8;
+    hipLaunchKernelGGL(k_vae_qknorm_bwd, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, s, dQKV, PRE, M, heads, norm);
+}
+
+}  // namespace geo
 
 extern "C" int64_t foho_vae_abi_size(void) { return (int64_t)sizeof(foho_vae_layer) * 1000 + (int64_t)sizeof(foho_vae_desc); }
 
@@ -229,8 +223,12 @@ extern "C" int foho_vae_fwd(const foho_vae_desc* d, const void* x0, void* out, v
         if (hipMemcpyAsync(keep + sv.x, x0, (size_t)M * W * 2, hipMemcpyDeviceToDevice, s) != hipSuccess) return fail(FOHO_ERR_LAUNCH, "foho_vae_fwd: copy failed");
         X = (const h16*)(keep + sv.x);
     }
-    hipLaunchKernelGGL(k_vae_rowstat, dim3((M + 3) / 4), dim3(256), 0, s, X, M, W, d->layers[0].eps1, rowstat);
+    vae_rowstat(s, X, M, W, d->layers[0].eps1, rowstat);
     if (!launch_ok("k_vae_rowstat")) return FOHO_ERR_LAUNCH;
+    // the attention of all images in ONE launch: 192 workgroups per image do not fill the chip
+    AttnFwd at;
+    at.ldq = at.ldk = 3 * W, at.Vt = vtB, at.L = Lt, at.ldo = W, at.M = Lt, at.heads = NH, at.qscale = QSCALE, at.images = B;
+    at.img.q = at.img.k = (long)Lt * 3 * W, at.img.vt = (long)W * Lt, at.img.o = (long)Lt * W, at.img.nlse = (long)Lt * NH;
     for (int i = 0; i < n; i++) {
         const foho_vae_layer& y = d->layers[i];
         char* rec = keep ? keep + (size_t)i * sv.per_layer : nullptr;
@@ -244,29 +242,27 @@ extern "C" int foho_vae_fwd(const foho_vae_desc* d, const void* x0, void* out, v
         h16* Xn = last ? (h16*)out : (h16*)(rec ? keep + (size_t)(i + 1) * sv.per_layer + sv.x : base + ((i & 1) ? l.xb : l.xa));
         // q | k | v behind the folded ln_1 (+ qk_norm; + the un-normalised projection when a backward will follow); the epilogue also leaves V^T
         // for the attention below and -- kept -- Qs, Qs^T, K^T for the backward's
-        EpiAux aq;
-        aq.vt = vtB, aq.lt = Lt, aq.ldqst = M, aq.qscale = SDPA_QSCALE;
-        if (rec) aq.qs = (h16*)(rec + sv.qs), aq.qst = (h16*)(rec + sv.qst), aq.kt = (h16*)(rec + sv.kt);
-        const int epq = EP_PREAFF | EP_PACK | (y.qk_norm ? EP_QKN : 0) | (PRE ? EP_SAVEZ : 0);
-        if (int rc = gemm(epq, X, W, (const h16*)y.w_qkv, W, y.fold_qkv, (const h16*)rowstat, 3 * W, QKV, 3 * W, M, 3 * W, W, 1.0f, s, PRE, 3 * W, nullptr, GV_AUTO, aq)) return rc;
-        {   // all images in ONE launch (blockIdx.y = image): 192 workgroups per image do not fill the chip
-            const long i3 = (long)Lt * 3 * W, iw = (long)Lt * W;
-            AttnB ab;
-            ab.a = i3, ab.b = i3, ab.c = (long)W * Lt, ab.d = iw, ab.e = (long)Lt * NH;
-            launch_attn(dim3(((Lt + AQ - 1) / AQ) * NH, B), s, QKV, 3 * W, QKV + W, 3 * W, (const h16*)vtB, Lt, O, W, Lt, NH, NLSE, (const int*)nullptr, 64, 64, SDPA_QSCALE,
-                        (float*)nullptr, ab);
-        }
+        Epi qkv(y.fold_qkv);
+        qkv.preaff(rowstat, 3 * W, y.qk_norm != 0);
+        qkv.pack(vtB, rec ? (h16*)(rec + sv.qs) : nullptr, rec ? (h16*)(rec + sv.qst) : nullptr, rec ? (h16*)(rec + sv.kt) : nullptr, Lt, M, QSCALE);
+        if (PRE) qkv.save_z(PRE, 3 * W);
+        if (int rc = gemm(dense(X, y.w_qkv, QKV, M, 3 * W, W), qkv, s)) return rc;
+        at.Q = QKV, at.K = QKV + W, at.O = O, at.nlse = NLSE;
+        attn_fwd(s, at);
         if (!launch_ok("foho_vae_fwd (attention)")) return FOHO_ERR_LAUNCH;
-        if (int rc = gemm(EP_RESID | EP_STATS, O, W, (const h16*)y.w_proj, W, y.b_proj, X, W, X1, W, M, W, W, 1.0f, s, (h16*)stats, parts)) return rc;
-        hipLaunchKernelGGL(k_geo_rowstat_finish, dim3((M + 15) / 16), dim3(256), 0, s, stats, parts, M, y.eps2, rowstat, (const int*)nullptr);
+        if (int rc = gemm(dense(O, y.w_proj, X1, M, W, W), Epi(y.b_proj).resid(X, W).stats(stats, parts), s)) return rc;
+        rowstat_finish(s, stats, parts, M, y.eps2, rowstat);
         if (!launch_ok("k_geo_rowstat_finish")) return FOHO_ERR_LAUNCH;
-        if (int rc = gemm(EP_GELU | EP_PREAFF | (Z ? EP_SAVEZ : 0), X1, W, (const h16*)y.w_fc1, W, y.fold_fc1, (const h16*)rowstat, F, H, F, M, F, W, 1.0f, s, Z, Z ? F : 0))
-            return rc;
-        if (int rc = gemm(last ? EP_RESID : (EP_RESID | EP_STATS), H, F, (const h16*)y.w_fc2, F, y.b_fc2, X1, W, Xn, W, M, W, F, 1.0f, s, last ? nullptr : (h16*)stats,
-                          last ? 0 : parts))
-            return rc;
+        Epi fc1(y.fold_fc1);
+        fc1.gelu().preaff(rowstat, F);
+        if (Z) fc1.save_z(Z, F);
+        if (int rc = gemm(dense(X1, y.w_fc1, H, M, F, W), fc1, s)) return rc;
+        Epi fc2(y.b_fc2);
+        fc2.resid(X1, W);
+        if (!last) fc2.stats(stats, parts);   // ... of the next layer's input
+        if (int rc = gemm(dense(H, y.w_fc2, Xn, M, W, F), fc2, s)) return rc;
         if (!last) {
-            hipLaunchKernelGGL(k_geo_rowstat_finish, dim3((M + 15) / 16), dim3(256), 0, s, stats, parts, M, d->layers[i + 1].eps1, rowstat, (const int*)nullptr);
+            rowstat_finish(s, stats, parts, M, d->layers[i + 1].eps1, rowstat);
             if (!launch_ok("k_geo_rowstat_finish")) return FOHO_ERR_LAUNCH;
         }
         X = Xn;
@@ -294,10 +290,17 @@ extern "C" int foho_vae_bwd(const foho_vae_desc* d, const void* grad_out, void* 
     float* deltaB = (float*)(base + l.deltab);
     // enough (image, head, key block) workgroups to fill the chip on their own: each writes its dK / dV itself, all images in one launch
     const bool direct = !(d->flags & FOHO_VAE_SPLIT_DKV) && (long)B * NH * (Lt / 128) >= 256;
-    const float* nof = nullptr;
     const float* nog = nullptr;   // gamma = 1: the gradients come through the folded weights
-    const dim3 rows((M + 3) / 4), blk(256);
     const h16* G = (const h16*)grad_out;
+    // the attention backward of all images: what does not depend on the layer
+    const long i3 = (long)Lt * 3 * W, iw = (long)Lt * W, ih = (long)Lt * NH;
+    AttnBwd bk;
+    bk.dO = dO, bk.dOT = dOT, bk.ldt = M, bk.ndelta = deltaB, bk.ldkv = 3 * W, bk.width = W, bk.heads = NH, bk.M = Lt, bk.L = Lt, bk.images = B;
+    bk.dk16 = dQKV + W, bk.dv16 = dQKV + 2 * W, bk.ld16 = 3 * W;
+    bk.img.qs = iw, bk.img.qst = Lt, bk.img.dO = iw, bk.img.dOT = Lt, bk.img.nlse = ih, bk.img.ndelta = ih, bk.img.kv = i3, bk.img.dkv = i3;
+    AttnDq dq;
+    dq.dO = dO, dq.ldq = W, dq.ldkv = 3 * W, dq.width = W, dq.L = Lt, dq.ndelta = deltaB, dq.dQ = dQKV, dq.lddq = 3 * W, dq.M = Lt, dq.heads = NH, dq.images = B;
+    dq.img.qs = iw, dq.img.dO = iw, dq.img.kv = i3, dq.img.kt = (long)W * Lt, dq.img.nlse = ih, dq.img.ndelta = ih, dq.img.dq = i3;
     for (int i = n - 1; i >= 0; i--) {
         const foho_vae_layer& y = d->layers[i];
         const char* rec = keep + (size_t)i * sv.per_layer;
@@ -306,39 +309,26 @@ extern "C" int foho_vae_bwd(const foho_vae_desc* d, const void* grad_out, void* 
         const float* NLSE = (const float*)(rec + sv.nlse);
         const h16 *qsB = (const h16*)(rec + sv.qs), *QsT = (const h16*)(rec + sv.qst), *ktB = (const h16*)(rec + sv.kt);
         h16* Gn = (i == 0) ? (h16*)grad_x0 : GB;
-        if (int rc = gemm(EP_GELUBWD, G, W, (const h16*)y.w_fc2_t, W, d->zeros, Z, F, H, F, M, F, W, 1.0f, s)) return rc;           // dZ
-        if (int rc = gemm(0, H, F, (const h16*)y.w_fc1_t, F, d->zeros, nullptr, 0, T1, W, M, W, F, 1.0f, s)) return rc;             // d / d xhat of ln_2
-        hipLaunchKernelGGL(k_geo_ln_bwd<0>, rows, blk, 0, s, X1, nog, (const h16*)T1, G, nof, 0.0f, nof, G1, M, W, y.eps2, (const int*)nullptr);
+        if (int rc = gemm(dense(G, y.w_fc2_t, H, M, F, W), Epi(d->zeros).gelu_bwd(Z, F), s)) return rc;   // dZ
+        if (int rc = gemm(dense(H, y.w_fc1_t, T1, M, W, F), Epi(d->zeros), s)) return rc;                 // d / d xhat of ln_2
+        ln_rows_bwd(s, X1, nog, y.eps2, T1, G, G1, M, W);
         if (!launch_ok("k_geo_ln_bwd(2)")) return FOHO_ERR_LAUNCH;
-        EpiAux ad;
-        ad.ndelta = deltaB, ad.heads = NH;
-        if (int rc = gemm(EP_TRANS | EP_DELTA, G1, W, (const h16*)y.w_proj_t, W, d->zeros, O, W, dO, W, M, W, W, 1.0f, s, dOT, M, nullptr, GV_AUTO, ad)) return rc;   // dO, dO^T, delta
-        if (direct) {   // all images in one launch per kernel (blockIdx.y / .z = image)
-            const long i3 = (long)Lt * 3 * W, iw = (long)Lt * W, ih = (long)Lt * NH, it = (long)W * Lt;
-            const int nkb = Lt / 128;
-            AttnB bk, dq;
-            bk.a = iw, bk.b = Lt, bk.c = iw, bk.d = Lt, bk.e = ih, bk.f = ih, bk.g = i3, bk.h = i3;
-            dq.a = iw, dq.b = iw, dq.c = i3, dq.d = it, dq.e = ih, dq.f = ih, dq.g = i3;
-            hipLaunchKernelGGL(k_geo_attn_bwd, dim3(8 * ((NH + 7) / 8) * nkb, B), blk, 0, s, qsB, QsT, (const h16*)dO, (const h16*)dOT, M, NLSE, (const float*)deltaB, QKV + W, 3 * W, W, NH,
-                               Lt, 1, Lt, 0, (float*)nullptr, (const int*)nullptr, QKV + 2 * W, 64, dQKV + W, dQKV + 2 * W, 3 * W, bk);
-            hipLaunchKernelGGL(k_geo_attn_dq, dim3(((Lt + DQQ - 1) / DQQ) * NH, B), blk, 0, s, qsB, (const h16*)dO, W, QKV + W, 3 * W, W, ktB, Lt, NLSE, (const float*)deltaB, dQKV, Lt, NH,
-                               QKV + 2 * W, 64, 3 * W, dq);
+        if (int rc = gemm(dense(G1, y.w_proj_t, dO, M, W, W), Epi(d->zeros).trans(dOT, M).delta(O, W, deltaB, NH), s)) return rc;   // dO, dO^T, delta
+        bk.Qs = dq.Qs = qsB, bk.QsT = QsT, dq.Kt = ktB, bk.nlse = dq.nlse = NLSE, bk.KV = dq.KV = QKV + W, bk.Vp = dq.Vp = QKV + 2 * W;
+        if (direct) {   // all images in one launch per kernel
+            attn_bwd(s, bk);
+            attn_dq(s, dq);
             if (!launch_ok("vae attention backward")) return FOHO_ERR_LAUNCH;
-        } else {
-            for (int b = 0; b < B; b++) {
-                const size_t r0 = (size_t)b * Lt;
-                if (int rc = vae_attn_bwd_image(l.sl, base + l.sdpa, QKV + r0 * 3 * W, 3 * W, dO + r0 * W, NLSE + r0 * NH, dQKV + r0 * 3 * W, qsB + r0 * W, QsT + r0, dOT + r0, M,
-                                                ktB + (size_t)b * W * Lt, deltaB + r0 * NH, Lt, NH, s))
-                    return rc;
-            }
+        } else {   // (too few (head, key block) workgroups to fill the chip, or FOHO_VAE_SPLIT_DKV): image by image through the stand-alone attention's scratch
+            for (int b = 0; b < B; b++)
+                if (int rc = attn_bwd_split(s, image_of(bk, b), image_of(dq, b), l.sl.splits, (float*)(base + l.sdpa + l.sl.part))) return rc;
         }
         if (y.qk_norm) {   // (inside the two kernels' way out it cost them 6-9 us each against the 8 us of this launch: NOTEBOOK round 6)
-            const size_t lanes = (size_t)M * 2 * NH * 8;
-            hipLaunchKernelGGL(k_vae_qknorm_bwd, dim3((unsigned)((lanes + 255) / 256)), blk, 0, s, dQKV, PRE, M, NH, y.fold_qkv + 6 * W);
+            vae_qknorm_bwd(s, dQKV, PRE, M, NH, y.fold_qkv + 6 * W);
             if (!launch_ok("k_vae_qknorm_bwd")) return FOHO_ERR_LAUNCH;
         }
-        if (int rc = gemm(0, dQKV, 3 * W, (const h16*)y.w_qkv_t, 3 * W, d->zeros, nullptr, 0, T1, W, M, W, 3 * W, 1.0f, s)) return rc;   // d / d xhat of ln_1
-        hipLaunchKernelGGL(k_geo_ln_bwd<0>, rows, blk, 0, s, X, nog, (const h16*)T1, (const h16*)G1, nof, 0.0f, nof, Gn, M, W, y.eps1, (const int*)nullptr);
+        if (int rc = gemm(dense(dQKV, y.w_qkv_t, T1, M, W, 3 * W), Epi(d->zeros), s)) return rc;   // d / d xhat of ln_1
+        ln_rows_bwd(s, X, nog, y.eps1, T1, G1, Gn, M, W);
         if (!launch_ok("k_geo_ln_bwd(1)")) return FOHO_ERR_LAUNCH;
         G = Gn;
     }
