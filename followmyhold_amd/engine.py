@@ -9,10 +9,22 @@ src/foho/configs/guid_config.py (CFG) of the reference:
   phase "A"  hand only    PL:1320-1349, Adam  (CFG phase1_hand_lrs)
   phase "B"  object only  PL:1386-1440, AdamW (CFG obj_2half_lrs)
   phase "C"  joint        PL:1480-1588, AdamW (CFG phase2_hand_lrs + obj_lrs)  <- the "guidance step"
+
+The host side has one writer per decision:
+  pack_scenes           scene dicts -> host arrays (image records, meta, vertices, faces, masks, identity parameters,
+                        hand-order table ...), pure numpy / ctypes; GuidanceBatch.__init__ allocates device tensors from
+                        its output, load_scenes uploads its output into the existing ones
+  write_camera          the camera part of an image record (the packer, TargetRenderer.render_into)
+  _set_object_sizes     every place a one-object batch keeps its sizes (update_object, TargetRenderer.render_into)
+  _upload               page-locked mirrors and their event (load_scenes, the hand-order table of a new workspace)
+  GuidanceBatch.step    the call of foho_step_run, with the per-input stages that are due (_take_due); prepare and
+                        refresh_* go through it
+  _optimiser_state_kept the warm-up launch in front of a capture (GuidanceBatch / SdfObjective / GuidanceGroup)
 """
+import contextlib
 import ctypes
 import os
-import math
+import types
 
 import numpy as np
 import torch
@@ -185,13 +197,127 @@ def morton_order(points):
 _WARMED_DEVICES = set()     # GPUs on which this process has launched the step once (GuidanceBatch.capture)
 
 
-def _same_regressor(jr, first_scene, b):
-    """A batch shares ONE joint regressor (foho_step_desc.J_regressor): an image that brings another one would silently be
-    regressed with the first image's."""
-    j0 = np.asarray(first_scene["J_regressor"], np.float32)
-    if jr.shape != j0.shape or not np.array_equal(jr, j0):
-        raise L.FohoError(f"GuidanceBatch: image {b} has a J_regressor that differs from image 0's; a batch shares one "
-                          "(put images of different hand models into different batches)")
+_NO_UPDATE_C = phase_cfg("C", do_update=False)[0]     # for launches of stages that read no weight (AABB, target sums, vertex stage)
+IDENTITY_PARAMS = np.array([1, 0, 0, 0, 1, 0, 0, 0] * 2, np.float32)      # PL:1207-1215: s=1, t=0, q=(1,0,0,0), hand then object
+
+
+def write_camera(im, fov, cam_R=None, cam_T=None):
+    """Camera part of an image record (FohoImage): pytorch3d's FoVPerspectiveCameras looking down -z (RUN:84-90)."""
+    im.k00, im.k11 = fov_focal(float(fov))
+    im.cam_R[:] = np.asarray(np.diag([-1.0, 1.0, -1.0]) if cam_R is None else cam_R, np.float32).reshape(-1).tolist()
+    im.cam_T[:] = np.asarray(np.zeros(3) if cam_T is None else cam_T, np.float32).reshape(-1).tolist()
+    im.znear, im.zfar = 0.01, 100.0
+
+
+def hand_order_table(hand_verts_per_image):
+    """Lane -> hand vertex table of the nearest-neighbour role (workspace region "hand_order", stored as a delta on the
+    lane slot): the hand's vertices in Morton order, so that a wave's 64 vertices are neighbours in space and agree more
+    often on the candidate runs they can skip (k_vertex.inc).  Any permutation gives the same results."""
+    tab = np.zeros((len(hand_verts_per_image), max([len(hv) for hv in hand_verts_per_image] + [1])), np.int32)
+    for b, hv in enumerate(hand_verts_per_image):
+        tab[b, :len(hv)] = morton_order(hv) - np.arange(len(hv))
+    return tab
+
+
+def _image_bytes(images):
+    return np.frombuffer(bytearray(b"".join(bytes(im) for im in images)), np.uint8)      # a bytearray: writable, as torch wants it
+
+
+def pack_scenes(scenes, capacity=None, install=False):
+    """Scene dicts (GuidanceBatch's docstring) -> the host arrays of a batch.  Pure numpy / ctypes: no device, no library.
+
+    capacity=None: EXACT SIZE, every image gets the vertex / face slots of its own object.  capacity=(vcap, fcap): every
+    image gets that many object slots; install=False leaves them empty (the scenes' own objects are ignored: a new batch
+    gets its objects from SdfObjective), install=True puts the scenes' objects into them (load_scenes).
+
+    Returns a namespace of B, H, W, Vtot, Ftot; images (FohoImage records; in capacity mode their Vo / Fo / n_edges are 0,
+    the device-side records get the actual counts from foho_object_update); meta; verts (Vtot, 3) float32; hand_faces
+    (per image, (Fh, 3) int32 global vertex ids); faces (Ftot, 3) int32 global vertex ids, what a new batch's `faces` starts
+    from (the rows of an empty capacity slot name the slot's first vertex; None with install=True: the rows of an installed
+    object are foho_object_update's); obj_faces64 (B, fcap, 3) int64
+    mesh-local and counts (B, 3) int32 (capacity mode, else None); J (the ONE regressor of the batch); mask (B, H, W) uint8,
+    bit 0 hand, bit 1 object; kps_2d; params (identity rows); hand_order; tgt_normal / tgt_disp (per-image lists, or None
+    when the scenes bring no target maps: a TargetRenderer fills them on the device).  n_edges of an exact-size image is
+    left 0: the edge count belongs to the topology tables, which the batch builds."""
+    B, H, W = len(scenes), int(scenes[0]["H"]), int(scenes[0]["W"])
+    assert all(int(s["H"]) == H and int(s["W"]) == W for s in scenes), "one image size per batch"
+    assert capacity is not None or not install, "install: capacity mode only"
+    J = np.asarray(scenes[0]["J_regressor"], np.float32)
+    if capacity is not None:
+        vcap, fcap = capacity
+        obj_faces64, counts = np.zeros((B, fcap, 3), np.int64), np.zeros((B, 3), np.int32)
+    images, meta, verts, faces, hand_faces = [], [], [], [], []
+    v_off = f_off = 0
+    for b, s in enumerate(scenes):
+        jr = np.asarray(s["J_regressor"], np.float32)
+        if jr.shape != J.shape or not np.array_equal(jr, J):      # it would silently be regressed with image 0's
+            raise L.FohoError(f"GuidanceBatch: image {b} has a J_regressor that differs from image 0's; a batch shares one "
+                              "(foho_step_desc.J_regressor: put images of different hand models into different batches)")
+        hv, hf = np.asarray(s["hand_verts"], np.float32).reshape(-1, 3), np.asarray(s["hand_faces"], np.int64).reshape(-1, 3)
+        ov, of = np.asarray(s["obj_verts"], np.float32).reshape(-1, 3), np.asarray(s["obj_faces"], np.int64).reshape(-1, 3)
+        Vh, Fh, Vo, Fo = len(hv), len(hf), len(ov), len(of)
+        im = L.FohoImage()
+        m = dict(v_off=v_off, Vh=Vh, f_off=f_off, Fh=Fh, n_edges=0, fov=float(s["fov"]))
+        if capacity is None:
+            slot_v, slot_f = ov, (of + (v_off + Vh)).astype(np.int32)
+            im.Vo, im.Fo = Vo, Fo
+        else:
+            slot_v = np.zeros((vcap, 3), np.float32)
+            slot_f = None if install else np.full((fcap, 3), v_off + Vh, np.int32)     # any vertex of the image will do: no face yet
+            if not install:
+                Vo = Fo = 0
+            elif Vo > vcap or Fo > fcap:
+                raise L.FohoError(f"image {b}: object of {Vo} vertices / {Fo} faces does not fit the capacity ({vcap} / {fcap})")
+            slot_v[:Vo] = ov[:Vo]
+            obj_faces64[b, :Fo] = of[:Fo]
+            counts[b, :2] = (Vo, Fo)
+            m.update(Vcap=vcap, Fcap=fcap, n_edges=3 * Fo // 2)     # foho_object_update accepts closed manifolds only
+        m.update(Vo=Vo, Fo=Fo)
+        im.v_off, im.Vh, im.f_off, im.Fh, im.jcols = v_off, Vh, f_off, Fh, jr.shape[1]
+        write_camera(im, s["fov"], s.get("cam_R"), s.get("cam_T"))
+        im.T_h2m[:] = np.asarray(s["T_h2m"], np.float32)[:3, :4].reshape(-1).tolist()
+        images.append(im)
+        meta.append(m)
+        verts += [hv, slot_v]
+        hand_faces.append((hf + v_off).astype(np.int32))
+        if not install:
+            faces += [hand_faces[-1], slot_f]
+        v_off += Vh + len(slot_v)
+        f_off += Fh + (Fo if capacity is None else fcap)
+    targets = all("moge_normal" in s for s in scenes)
+    return types.SimpleNamespace(
+        B=B, H=H, W=W, Vtot=v_off, Ftot=f_off, images=images, meta=meta, J=J,
+        verts=np.concatenate(verts, 0), hand_faces=hand_faces, faces=None if install else np.concatenate(faces, 0),
+        obj_faces64=obj_faces64 if capacity is not None else None, counts=counts if capacity is not None else None,
+        mask=np.stack([np.asarray(s["hand_mask"]).astype(np.uint8) | (np.asarray(s["obj_mask"]).astype(np.uint8) << 1) for s in scenes]),
+        kps_2d=np.stack([np.asarray(s["kps_2d"], np.float32) for s in scenes]), params=np.tile(IDENTITY_PARAMS, (B, 1)),
+        hand_order=hand_order_table(verts[0::2]),      # `verts` alternates hand, object slot
+        tgt_normal=[s["moge_normal"] for s in scenes] if targets else None,
+        tgt_disp=[s["moge_disp"] for s in scenes] if targets else None)
+
+
+def _optimiser_state(gb):
+    return gb.params, gb.adam_m, gb.adam_v, gb.adam_t, gb.flags
+
+
+@contextlib.contextmanager
+def _optimiser_state_kept(batches, device, warm_stream=None):
+    """Around the warm-up launch that precedes a capture (the code object is loaded lazily, which a capture does not allow):
+    the launch's optimiser update is undone.  warm_stream: the stream the body launches on when that is ONE side stream; it
+    is ordered behind the current stream, and the current stream behind it.  Synchronises the device before the state is
+    restored and after."""
+    cur = torch.cuda.current_stream(device)
+    if warm_stream is not None:
+        warm_stream.wait_stream(cur)
+    saved = [[t.clone() for t in _optimiser_state(gb)] for gb in batches]
+    yield
+    if warm_stream is not None:
+        cur.wait_stream(warm_stream)
+    torch.cuda.synchronize(device)
+    for gb, sv in zip(batches, saved):
+        for t, s0 in zip(_optimiser_state(gb), sv):
+            t.copy_(s0)
+    torch.cuda.synchronize(device)
 
 
 class GuidanceBatch:
@@ -217,57 +343,23 @@ class GuidanceBatch:
         distances, silhouette products and every accumulation stay fp32."""
         self.lib = L.lib()
         self.device = torch.device(device)
-        self.B = B = len(scenes)
-        H, W = int(scenes[0]["H"]), int(scenes[0]["W"])
-        assert all(int(s["H"]) == H and int(s["W"]) == W for s in scenes), "one image size per batch"
-        self.H, self.W = H, W
         self.obj_capacity = None if obj_capacity is None else (int(obj_capacity[0]), int(obj_capacity[1]))
         if self.obj_capacity is not None:
-            vcap, fcap = self.obj_capacity
-            if vcap < 1 or fcap < 2:
+            if self.obj_capacity[0] < 1 or self.obj_capacity[1] < 2:
                 raise ValueError("obj_capacity: at least 1 vertex and 2 faces")
-            scenes = [dict(s, obj_verts=np.zeros((vcap, 3), np.float32), obj_faces=np.zeros((fcap, 3), np.int64)) for s in scenes]
             topology = "capacity"
-        verts, faces, images = [], [], []
-        v_off = f_off = 0
-        self.meta = []
-        for s in scenes:
-            hv, ov = np.asarray(s["hand_verts"], np.float32), np.asarray(s["obj_verts"], np.float32)
-            hf, of = np.asarray(s["hand_faces"], np.int64), np.asarray(s["obj_faces"], np.int64)
-            Vh, Vo, Fh, Fo = len(hv), len(ov), len(hf), len(of)
-            verts += [hv, ov]
-            faces += [hf + v_off, of + v_off + Vh]
-            im = L.FohoImage()
-            im.v_off, im.Vh, im.Vo, im.f_off, im.Fh, im.Fo = v_off, Vh, Vo, f_off, Fh, Fo
-            im.n_edges = 0
-            jr = np.asarray(s["J_regressor"], np.float32)
-            _same_regressor(jr, scenes[0], len(images))
-            im.jcols = jr.shape[1]
-            im.k00, im.k11 = fov_focal(float(s["fov"]))
-            R = np.asarray(s.get("cam_R", np.diag([-1.0, 1.0, -1.0])), np.float32).reshape(-1)  # RUN:84-90
-            T = np.asarray(s.get("cam_T", np.zeros(3)), np.float32)
-            for k in range(9):
-                im.cam_R[k] = float(R[k])
-            for k in range(3):
-                im.cam_T[k] = float(T[k])
-            im.znear, im.zfar = 0.01, 100.0
-            M = np.asarray(s["T_h2m"], np.float32)[:3, :4].reshape(-1)
-            for k in range(12):
-                im.T_h2m[k] = float(M[k])
-            images.append(im)
-            self.meta.append(dict(v_off=v_off, Vh=Vh, Vo=Vo, f_off=f_off, Fh=Fh, Fo=Fo, n_edges=0, fov=float(s["fov"])))
-            v_off += Vh + Vo
-            f_off += Fh + Fo
-        self.Vtot, self.Ftot = v_off, f_off
-        verts = np.concatenate(verts, 0)
-        faces = np.concatenate(faces, 0)
+        pk = pack_scenes(scenes, self.obj_capacity)
+        self.B, self.H, self.W, self.Vtot, self.Ftot = pk.B, pk.H, pk.W, pk.Vtot, pk.Ftot
+        self.meta, self._images_host = pk.meta, pk.images
+        B, H, W, images, faces = pk.B, pk.H, pk.W, pk.images, pk.faces
         dev = self.device
         t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(dt).to(dev)
-        self.verts_in = t(verts, torch.float32)
+        self.verts_in = t(pk.verts, torch.float32)
         self.faces = t(faces, torch.int32)
         obj_flag = np.zeros(self.Vtot, np.uint8)
-        for m in self.meta:
-            obj_flag[m["v_off"] + m["Vh"]:m["v_off"] + m["Vh"] + m["Vo"]] = 1
+        for b in range(B):
+            lo, n = self.obj_slot(b)
+            obj_flag[lo:lo + n] = 1
         ok = False
         if topology == "capacity":      # tables are (re)built on the device by foho_object_update; sized for the capacity
             ok = True
@@ -287,11 +379,7 @@ class GuidanceBatch:
             ok = self._device_topology(t(obj_flag, torch.uint8) if topology == "auto" else None)
             if ok and topology == "auto":
                 ok = all(m["Fo"] % 2 == 0 for m in self.meta)
-        if ok and topology == "capacity":
-            for m, im in zip(self.meta, images):     # no object yet: the records are filled in on the device
-                m.update(Vcap=m["Vo"], Fcap=m["Fo"], Vo=0, Fo=0)
-                im.Vo = im.Fo = im.n_edges = 0
-        elif ok:
+        if ok:      # (capacity mode: no object yet, 0 edges; the records are filled in on the device)
             for m, im in zip(self.meta, images):
                 m["n_edges"] = im.n_edges = (3 * m["Fo"] // 2) if topology == "auto" else 0
         else:   # general meshes (boundaries, non-manifold edges): sort-based builders on the host
@@ -308,23 +396,18 @@ class GuidanceBatch:
                 nbr_idx = np.zeros(1, np.int32)
             self.inc_off, self.inc_fc = t(inc_off, torch.int32), t(inc_fc, torch.int32)
             self.nbr_off, self.nbr_idx = t(nbr_off, torch.int32), t(nbr_idx, torch.int32)
-        self.J = t(np.asarray(scenes[0]["J_regressor"], np.float32), torch.float32)
-        self._images_host = images
-        img_bytes = b"".join(bytes(im) for im in images)
-        self.images = torch.frombuffer(bytearray(img_bytes), dtype=torch.uint8).to(dev)
-        if all("moge_normal" in s for s in scenes):
-            self.tgt_normal = t(np.stack([s["moge_normal"] for s in scenes]), torch.float32)
-            self.tgt_disp = t(np.stack([s["moge_disp"] for s in scenes]), torch.float32)
+        self.J = t(pk.J, torch.float32)
+        self.images = t(_image_bytes(images), torch.uint8)
+        if pk.tgt_normal is not None:
+            self.tgt_normal = t(np.stack(pk.tgt_normal), torch.float32)
+            self.tgt_disp = t(np.stack(pk.tgt_disp), torch.float32)
         else:       # target maps come from a TargetRenderer, on the device
             self.tgt_normal = torch.zeros(B, H, W, 3, device=dev)
             self.tgt_disp = torch.zeros(B, H, W, device=dev)
-        mask = np.stack([(np.asarray(s["hand_mask"]).astype(np.uint8) | (np.asarray(s["obj_mask"]).astype(np.uint8) << 1))
-                         for s in scenes])
-        self.mask = t(mask, torch.uint8)
-        self.kps_2d = t(np.stack([s["kps_2d"] for s in scenes]), torch.float32)
+        self.mask = t(pk.mask, torch.uint8)
+        self.kps_2d = t(pk.kps_2d, torch.float32)
 
-        ident = np.array([1, 0, 0, 0, 1, 0, 0, 0] * 2, np.float32)  # PL:1207-1215: s=1, t=0, q=(1,0,0,0)
-        self.params = t(np.tile(ident, (B, 1)), torch.float32)
+        self.params = t(pk.params, torch.float32)
         self.adam_m = torch.zeros(B, 16, device=dev)
         self.adam_v = torch.zeros(B, 16, device=dev)
         self.adam_t = torch.zeros(B, dtype=torch.int32, device=dev)
@@ -344,10 +427,9 @@ class GuidanceBatch:
         d.grid_res, d.frac_cap, d.n_renders = grid_res, frac_cap, n_renders
         d.gbuf_f16 = int(bool(gbuf_f16))     # BASELINE configs[4]: depth / colour planes of the G-buffer in fp16, sums in fp32
         self.dims = d
-        self._pinned, self._uploaded = {}, None      # page-locked upload mirrors of load_scenes()
-        self._hand_order = None
+        self._pinned, self._uploaded = {}, torch.cuda.Event()      # page-locked upload mirrors and the end of their last copies (_upload)
+        self._hand_order = pk.hand_order
         self._alloc_workspace()
-        self._set_hand_order([np.asarray(s["hand_verts"], np.float32) for s in scenes])
         if self.obj_capacity is not None:
             self.adopt_objects()        # hands only for now: tables, pair table and AABB of the (still empty) scene
             self.flags.zero_()          # ... which is not an "empty iso-surface" event (flag bit 6)
@@ -358,46 +440,42 @@ class GuidanceBatch:
         self.workspace = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
         self._desc = None
         # the AABB of verts_in lives in the workspace (FOHO_STAGE_BBOX); capacity mode recomputes it in adopt_objects()
-        self._bbox_dirty = getattr(self, "obj_capacity", None) is None
+        self._bbox_dirty = self.obj_capacity is None
         self._targets_dirty = True   # ... and so do the static loss sums of the target maps (FOHO_STAGE_TARGETS)
-        if getattr(self, "_hand_order", None) is not None:
-            self._upload_hand_order()
+        self._upload(("hand_order", self._hand_order_region(), self._hand_order))      # ... and the hand-order table
 
-    def _set_hand_order(self, hand_verts_per_image):
-        """Lane -> hand vertex table of the nearest-neighbour role (workspace region "hand_order", stored as a delta on the
-        lane slot): the hand's vertices in Morton order, so that a wave's 64 vertices are neighbours in space and agree more
-        often on the candidate runs they can skip (k_vertex.inc).  Any permutation gives the same results."""
-        vh_max = max(int(self.dims.Vh_max), 1)
-        tab = np.zeros((self.B, vh_max), np.int32)
-        for b, hv in enumerate(hand_verts_per_image):
-            n = len(hv)
-            if n:
-                tab[b, :n] = morton_order(hv) - np.arange(n)
-        self._hand_order = tab
-        self._desc = None                 # hand_order_valid / hand_faces_per_block are derived fields of the descriptor
-        self._upload_hand_order()
+    def _hand_order_region(self):
+        return self.region("hand_order", torch.int32, self._hand_order.shape)
 
-    def _upload_hand_order(self):
-        reg = self.region("hand_order", torch.int32, self._hand_order.shape)
-        buf = self._pinned.get("hand_order")
-        if buf is None or tuple(buf.shape) != tuple(self._hand_order.shape):
-            buf = self._pinned["hand_order"] = torch.empty(self._hand_order.shape, dtype=torch.int32, pin_memory=True)
-        if self._uploaded is not None:
-            self._uploaded.synchronize()
-        buf.numpy()[...] = self._hand_order
-        reg.copy_(buf, non_blocking=True)
-        if self._uploaded is None:
-            self._uploaded = torch.cuda.Event()
+    def _upload(self, *items):
+        """(key, dst, src) ...: host arrays into device tensors through page-locked mirrors owned by this batch, ASYNCHRONOUS
+        on the current stream: the host does not wait behind whatever that stream still has queued
+        (inputs.MeshGuidanceRunner keeps a second slot's whole job queued on it).  The mirrors are rewritten only after the
+        copies of the previous call have run (`_uploaded`: waited for before the first rewrite, recorded after the last
+        copy).  src: an array of dst's size, or a list with one array per image (written straight into the mirror)."""
+        self._uploaded.synchronize()
+        for key, dst, src in items:
+            buf = self._pinned.get(key)
+            if buf is None or buf.shape != dst.shape:
+                buf = self._pinned[key] = torch.empty(dst.shape, dtype=dst.dtype, pin_memory=True)
+            view = buf.numpy()
+            if isinstance(src, list):
+                for b, a in enumerate(src):
+                    view[b] = a
+            else:
+                view[...] = np.asarray(src).reshape(view.shape)
+            dst.copy_(buf, non_blocking=True)
         self._uploaded.record()
+
+    def _stream(self, stream=None):
+        return L._stream(self.device) if stream is None else stream
 
     def adopt_objects(self, stream=None):
         """Capacity mode: install the object meshes whose vertices sit in the object slots of verts_in, whose mesh-local
         faces sit in obj_faces64 and whose counts sit in obj_counts (all on the device, as foho_flexi_fwd leaves them):
         image records, global face ids, topology tables, pair table, AABB.  Asynchronous, no host round trip."""
-        if stream is None:
-            stream = L._stream(self.device)
         L.check(self.lib.foho_object_update(ctypes.byref(self.desc()), L._p(self.obj_counts), L._p(self.obj_faces64), self.obj_capacity[1],
-                                            L._p(self.obj_flag), L._p(self.obj_ws), self.obj_ws.numel(), stream), "foho_object_update")
+                                            L._p(self.obj_flag), L._p(self.obj_ws), self.obj_ws.numel(), self._stream(stream)), "foho_object_update")
 
     def obj_slot(self, b):
         """(first vertex slot, vertex capacity) of image b's object in verts_in / grad_verts_in."""
@@ -422,10 +500,9 @@ class GuidanceBatch:
                 setattr(d, name, getattr(self, name).data_ptr())
             d.J_regressor = self.J.data_ptr()
             d.workspace_bytes = self.workspace.numel()
-            d.hand_order_valid = int(getattr(self, "_hand_order", None) is not None)   # the table is (re-)uploaded with every workspace
+            d.hand_order_valid = 1          # the table is (re-)uploaded with every workspace (_alloc_workspace)
             # crops (the reference's frames: fov ~ 25 degrees, big hand faces): 2 hand faces per raster workgroup at one image
-            fovs = [float(m["fov"]) for m in self.meta if "fov" in m]
-            d.hand_faces_per_block = 2 if (self.B == 1 and fovs and max(fovs) < 40.0) else 0
+            d.hand_faces_per_block = 2 if (self.B == 1 and self.meta[0]["fov"] < 40.0) else 0
             self._desc = d
         return self._desc
 
@@ -440,30 +517,28 @@ class GuidanceBatch:
     def prepare(self, stream=None):
         """Run the per-input stages the step relies on (AABB / pair table / clean planes: FOHO_STAGE_BBOX; static sums of the
         target maps: FOHO_STAGE_TARGETS) now, eagerly, if they are due -- a captured hipGraph only holds the step itself."""
-        stages = 0
-        if self._bbox_dirty:
-            stages |= L.STAGE_BBOX
+        due = self._take_due(L.STAGE_VERTEX | L.STAGE_LOSS)
+        if due:
+            self.step(_NO_UPDATE_C, due, stream)
+
+    def _take_due(self, stages):
+        """The per-input stages that are due and that `stages` need (the vertex stage the AABB, the loss stage the target
+        sums) or name themselves.  The caller launches them: they are no longer due."""
+        due = 0
+        if self._bbox_dirty and stages & (L.STAGE_VERTEX | L.STAGE_BBOX):
+            due |= L.STAGE_BBOX
             self._bbox_dirty = False
-        if self._targets_dirty:
-            stages |= L.STAGE_TARGETS
+        if self._targets_dirty and stages & (L.STAGE_LOSS | L.STAGE_TARGETS):
+            due |= L.STAGE_TARGETS
             self._targets_dirty = False
-        if stages:
-            if stream is None:
-                stream = L._stream(self.device)
-            cfg, _ = phase_cfg("C", do_update=False)
-            L.check(self.lib.foho_step_run(ctypes.byref(self.desc()), ctypes.byref(cfg), int(stages), stream),
-                    "foho_step_run(prepare)")
+        return due
 
     def refresh_world(self, stream=None):
         """Recompute the world-space vertices (workspace region "world") from the CURRENT parameters.  A step transforms the
         vertices first and updates the parameters last, so after a loop the region is one optimiser update behind; the
         reference builds its output meshes from the final parameters (PL:1614-1618, 1653-1657).  One vertex-stage call."""
-        if stream is None:
-            stream = L._stream(self.device)
         self.prepare(stream)
-        cfg, _ = phase_cfg("C", do_update=False)
-        L.check(self.lib.foho_step_run(ctypes.byref(self.desc()), ctypes.byref(cfg), int(L.STAGE_VERTEX), stream),
-                "foho_step_run(VERTEX)")
+        self.step(_NO_UPDATE_C, L.STAGE_VERTEX, stream)
 
     def fits(self, scenes):
         """True when `scenes` can be loaded into this (capacity-mode) batch in place."""
@@ -488,93 +563,28 @@ class GuidanceBatch:
         if not self.fits(scenes):
             raise L.FohoError("load_scenes: needs a capacity-mode batch and scenes of the same image size / hand topology "
                               "whose objects fit the capacity")
-        dev = self.device
-        vcap, fcap = self.obj_capacity
-        verts = np.zeros((self.Vtot, 3), np.float32)
-        hfaces = []
-        faces64 = np.zeros((self.B, fcap, 3), np.int64)
-        counts = np.zeros((self.B, 3), np.int32)
-        for b, (s, m, im) in enumerate(zip(scenes, self.meta, self._images_host)):
-            ov, of = np.asarray(s["obj_verts"], np.float32).reshape(-1, 3), np.asarray(s["obj_faces"], np.int64).reshape(-1, 3)
-            nv, nf = len(ov), len(of)
-            lo = m["v_off"]
-            verts[lo:lo + m["Vh"]] = np.asarray(s["hand_verts"], np.float32)
-            verts[lo + m["Vh"]:lo + m["Vh"] + nv] = ov
-            hfaces.append(np.asarray(s["hand_faces"], np.int64) + lo)
-            faces64[b, :nf] = of
-            counts[b, :2] = (nv, nf)
-            m.update(Vo=nv, Fo=nf, n_edges=3 * nf // 2, fov=float(s["fov"]))
-            im.k00, im.k11 = fov_focal(float(s["fov"]))
-            R = np.asarray(s.get("cam_R", np.diag([-1.0, 1.0, -1.0])), np.float32).reshape(-1)
-            T = np.asarray(s.get("cam_T", np.zeros(3)), np.float32)
-            M = np.asarray(s["T_h2m"], np.float32)[:3, :4].reshape(-1)
-            for k in range(9):
-                im.cam_R[k] = float(R[k])
-            for k in range(3):
-                im.cam_T[k] = float(T[k])
-            for k in range(12):
-                im.T_h2m[k] = float(M[k])
-            im.Vo = im.Fo = im.n_edges = 0        # the device-side records get the actual counts from foho_object_update
-        # Uploads go through page-locked mirrors owned by this batch and are ASYNCHRONOUS on the current stream: the host does
-        # not wait behind whatever that stream still has queued (inputs.MeshGuidanceRunner keeps a second slot's whole job
-        # queued on it).  A mirror is rewritten only after the copies of the previous load have run (`_uploaded`).
-        if self._uploaded is not None:
-            self._uploaded.synchronize()
-
-        def up(key, dst, fill):
-            buf = self._pinned.get(key)
-            if buf is None:
-                buf = self._pinned[key] = torch.empty(dst.shape, dtype=dst.dtype, pin_memory=True)
-            fill(buf.numpy())
-            dst.copy_(buf, non_blocking=True)
-
-        def put(a):
-            def fill(view):
-                view[...] = np.asarray(a).reshape(view.shape)
-            return fill
-
-        def per_image(get):
-            def fill(view):
-                for b, s in enumerate(scenes):
-                    view[b] = get(s)
-            return fill
-
-        up("verts", self.verts_in, put(verts))
-        for b, (m, hf) in enumerate(zip(self.meta, hfaces)):
-            up(("hand_faces", b), self.faces[m["f_off"]:m["f_off"] + m["Fh"]], put(hf))
-        up("obj_faces", self.obj_faces64, put(faces64))
-        up("counts", self.obj_counts, put(counts))
-        up("images", self.images, put(np.frombuffer(b"".join(bytes(im) for im in self._images_host), np.uint8)))
-        if all("moge_normal" in s for s in scenes):      # else: the caller renders them into tgt_normal / tgt_disp (TargetRenderer)
-            up("tgt_normal", self.tgt_normal, per_image(lambda s: s["moge_normal"]))
-            up("tgt_disp", self.tgt_disp, per_image(lambda s: s["moge_disp"]))
-        up("mask", self.mask, per_image(lambda s: np.asarray(s["hand_mask"]).astype(np.uint8) | (np.asarray(s["obj_mask"]).astype(np.uint8) << 1)))
-        up("kps", self.kps_2d, per_image(lambda s: s["kps_2d"]))
-        # the joint regressor is shared by the batch (foho_step_desc.J_regressor; MANO's is a constant of the hand model): the new
-        # image set's, not the first set's -- and one for all of its images, or the set is refused
-        for b, s in enumerate(scenes):
-            _same_regressor(np.asarray(s["J_regressor"], np.float32), scenes[0], b)
-        up("J", self.J, put(np.asarray(scenes[0]["J_regressor"], np.float32)))
+        # the new set's own regressor -- one for all of its images, or the packer refuses the set before anything is touched
+        pk = pack_scenes(scenes, self.obj_capacity, install=True)
+        for m, new in zip(self.meta, pk.meta):
+            m.update(new)
+        self._images_host, self._hand_order = pk.images, pk.hand_order
         self._desc = None                 # the descriptor's derived fields (faces per raster workgroup: by field of view) follow the new set
-        up("params", self.params, put(np.tile(np.array([1, 0, 0, 0, 1, 0, 0, 0] * 2, np.float32), (self.B, 1))))
-        vh_max = max(int(self.dims.Vh_max), 1)
-
-        def order(view):
-            view[...] = 0
-            for b, s in enumerate(scenes):
-                n = len(s["hand_verts"])
-                view[b, :n] = morton_order(s["hand_verts"]) - np.arange(n)
-            self._hand_order = view.copy()
-        up("hand_order", self.region("hand_order", torch.int32, (self.B, vh_max)), order)
-        if self._uploaded is None:
-            self._uploaded = torch.cuda.Event()
-        self._uploaded.record()
+        ups = [("verts", self.verts_in, pk.verts)]
+        for b, m in enumerate(self.meta):       # the object rows of `faces` are foho_object_update's
+            ups.append((("hand_faces", b), self.faces[m["f_off"]:m["f_off"] + m["Fh"]], pk.hand_faces[b]))
+        ups += [("obj_faces", self.obj_faces64, pk.obj_faces64), ("counts", self.obj_counts, pk.counts),
+                ("images", self.images, _image_bytes(pk.images))]
+        if pk.tgt_normal is not None:      # else: the caller renders them into tgt_normal / tgt_disp (TargetRenderer)
+            ups += [("tgt_normal", self.tgt_normal, pk.tgt_normal), ("tgt_disp", self.tgt_disp, pk.tgt_disp)]
+        ups += [("mask", self.mask, pk.mask), ("kps", self.kps_2d, pk.kps_2d), ("J", self.J, pk.J), ("params", self.params, pk.params),
+                ("hand_order", self._hand_order_region(), pk.hand_order)]
+        self._upload(*ups)
         self.reset_optimizer()
         self.adopt_objects()
         self.load_flags = self.flags.clone()
         self.flags.zero_()
         self._targets_dirty = True
-        if all("moge_normal" in s for s in scenes):
+        if pk.tgt_normal is not None:
             self.prepare()
 
     # ------------------------------------------------------------------ state
@@ -602,12 +612,18 @@ class GuidanceBatch:
     def refresh_bbox(self, stream=None):
         """Recompute the AABB of the input meshes (centre of the similarity transform, PL:111).  Needed once and after
         every change of verts_in; the per-iteration step (STAGE_STEP) reuses it."""
-        if stream is None:
-            stream = L._stream(self.device)
-        cfg, _ = phase_cfg("C", do_update=False)
-        L.check(self.lib.foho_step_run(ctypes.byref(self.desc()), ctypes.byref(cfg), int(L.STAGE_BBOX), stream),
-                "foho_step_run(BBOX)")
-        self._bbox_dirty = False
+        self.step(_NO_UPDATE_C, L.STAGE_BBOX, stream)
+
+    def _set_object_sizes(self, Vo, Fo):
+        """One-image batch: the object has `Vo` vertices and `Fo` faces from now on -- in meta, the host image record (whose
+        upload is the caller's), Vtot / Ftot, dims and the descriptor, which is built anew.  The edge count is the topology
+        tables' (0 until they say otherwise); buffers and workspace stay as they are."""
+        m, im, d = self.meta[0], self._images_host[0], self.dims
+        m.update(Vo=Vo, Fo=Fo, n_edges=0)
+        im.Vo, im.Fo, im.n_edges = Vo, Fo, 0
+        self.Vtot, self.Ftot = m["Vh"] + Vo, m["Fh"] + Fo
+        d.Vtot, d.Ftot, d.Vmax, d.Fmax, d.Vo_max, d.Fo_max = self.Vtot, self.Ftot, self.Vtot, self.Ftot, Vo, Fo
+        self._desc = None
 
     def update_object(self, verts, faces, assume_manifold=True):
         """New object mesh with a NEW TOPOLOGY (the FlexiCubes output of this iteration, PL:1393 / 1509) for a one-image
@@ -623,14 +639,14 @@ class GuidanceBatch:
         dev = self.device
         v = torch.as_tensor(verts, dtype=torch.float32, device=dev).detach().reshape(-1, 3).contiguous()
         f = torch.as_tensor(faces, device=dev).detach().to(torch.int64).reshape(-1, 3)
-        m = self.meta[0]
+        m, im = self.meta[0], self._images_host[0]
         Vh, Fh = m["Vh"], m["Fh"]
         Vo, Fo = int(v.shape[0]), int(f.shape[0])
         Vtot, Ftot = Vh + Vo, Fh + Fo
         self.verts_in = torch.cat([self.verts_in[:Vh], v], 0).contiguous()
         faces_all = torch.cat([self.faces[:Fh].to(torch.int64), f + Vh], 0)
         self.faces = faces_all.to(torch.int32).contiguous()
-        self.Vtot, self.Ftot = Vtot, Ftot          # _device_topology sizes its tables from these
+        self._set_object_sizes(Vo, Fo)             # first: _device_topology sizes its tables from Vtot
         n_edges = -1
         if assume_manifold and Fo > 0 and Fo % 2 == 0:
             # dual-marching-cubes output is a closed oriented 2-manifold: tables straight from the incidence lists
@@ -642,21 +658,14 @@ class GuidanceBatch:
         if n_edges < 0:
             self._topology_by_sort(faces_all, f, Vh, Vtot, Ftot)
             n_edges = self._n_edges
-        # image record, sizes, outputs
-        im = self._images_host[0]
-        im.Vo, im.Fo, im.n_edges = Vo, Fo, n_edges
-        self.images = torch.frombuffer(bytearray(bytes(im)), dtype=torch.uint8).to(dev)
-        m.update(Vo=Vo, Fo=Fo, n_edges=n_edges)
-        self.Vtot, self.Ftot = Vtot, Ftot
-        d = self.dims
-        d.Vtot, d.Ftot, d.Vmax, d.Fmax, d.Vo_max, d.Fo_max = Vtot, Ftot, Vtot, Ftot, Vo, Fo
+        m["n_edges"] = im.n_edges = n_edges
+        self.images = torch.from_numpy(_image_bytes([im])).to(dev)
         self.grad_verts_in = torch.zeros(Vtot, 3, device=dev)
-        need = int(self.lib.foho_step_workspace_bytes(ctypes.byref(d)))
+        need = int(self.lib.foho_step_workspace_bytes(ctypes.byref(self.dims)))
         if need > self.workspace.numel():
             self.workspace = torch.zeros(int(need * 1.25), dtype=torch.uint8, device=dev)   # head-room: sizes drift slowly
             self._targets_dirty = True
-        self._desc = None
-        self._bbox_dirty = True     # the workspace layout moved with the sizes: AABB + clean scatter planes again
+        self._bbox_dirty = True    # the workspace layout moved with the sizes: AABB + clean scatter planes again
 
     def _device_topology(self, obj_flag):
         """foho_topology_tables on self.faces: incidence lists (+ neighbour lists at the same offsets when obj_flag marks the
@@ -718,16 +727,10 @@ class GuidanceBatch:
 
     # ------------------------------------------------------------------ the step
     def step(self, cfg, stages=L.STAGE_STEP, stream=None):
-        """One iteration for every image of the batch; asynchronous on the current stream."""
-        if stream is None:
-            stream = L._stream(self.device)
-        if self._bbox_dirty and (stages & L.STAGE_VERTEX):
-            stages |= L.STAGE_BBOX
-            self._bbox_dirty = False
-        if self._targets_dirty and (stages & L.STAGE_LOSS):
-            stages |= L.STAGE_TARGETS
-            self._targets_dirty = False
-        L.check(self.lib.foho_step_run(ctypes.byref(self.desc()), ctypes.byref(cfg), int(stages), stream),
+        """One iteration for every image of the batch -- or the `stages` of one --, together with the per-input stages they
+        need and that are due; asynchronous on `stream` (default: the current one).  The one call of foho_step_run."""
+        stages |= self._take_due(stages)
+        L.check(self.lib.foho_step_run(ctypes.byref(self.desc()), ctypes.byref(cfg), int(stages), self._stream(stream)),
                 "foho_step_run")
 
     def loss_dict(self, b=0):
@@ -773,15 +776,8 @@ class GuidanceBatch:
             # first capture of the process on this GPU: one launch outside capture (the code object is loaded lazily, which a
             # capture does not allow); its optimiser update is undone.  The only device-wide synchronisation of a capture.
             s = torch.cuda.Stream(self.device)
-            s.wait_stream(torch.cuda.current_stream(self.device))
-            state = [t.clone() for t in (self.params, self.adam_m, self.adam_v, self.adam_t, self.flags)]
-            with torch.cuda.stream(s):
+            with _optimiser_state_kept([self], self.device, warm_stream=s), torch.cuda.stream(s):
                 self.step(cfg)
-            torch.cuda.current_stream(self.device).wait_stream(s)
-            torch.cuda.synchronize(self.device)
-            for t, saved in zip((self.params, self.adam_m, self.adam_v, self.adam_t, self.flags), state):
-                t.copy_(saved)
-            torch.cuda.synchronize(self.device)
             _WARMED_DEVICES.add(dev_index)
         # Several iterations in one graph: every iteration but the last leaves its final stage (loss assembly, parameter
         # gradients, Adam) to the prologue of the next one (foho_step_cfg.deferred_update) -- the serial last-workgroup
@@ -808,9 +804,7 @@ class GuidanceBatch:
 
     def finalize(self, cfg, stream=None):
         """Apply the update a deferred_update step left pending (no-op when nothing is pending)."""
-        if stream is None:
-            stream = L._stream(self.device)
-        L.check(self.lib.foho_step_finalize(ctypes.byref(self.desc()), ctypes.byref(cfg), stream),
+        L.check(self.lib.foho_step_finalize(ctypes.byref(self.desc()), ctypes.byref(cfg), self._stream(stream)),
                 "foho_step_finalize")
 
     def step_profiled(self, cfg, deferred=False):
@@ -821,12 +815,11 @@ class GuidanceBatch:
         lib = self.lib
         self.prepare()
         ms = (ctypes.c_float * L.N_KERNELS)()
-        stream = L._stream(self.device)
         c2 = cfg
         if deferred:
             c2 = L.FohoStepCfg.from_buffer_copy(bytes(cfg))
             c2.deferred_update = 2
-        L.check(lib.foho_step_run_profiled(ctypes.byref(self.desc()), ctypes.byref(c2), stream, ms),
+        L.check(lib.foho_step_run_profiled(ctypes.byref(self.desc()), ctypes.byref(c2), self._stream(), ms),
                 "foho_step_run_profiled")
         names = [lib.foho_kernel_name(i).decode() for i in range(L.N_KERNELS)]
         out = {n: float(ms[i]) for i, n in enumerate(names) if n}
@@ -901,14 +894,8 @@ class SdfObjective:
         if g is None:
             gb = self.gb
             st = self._stream
-            st.wait_stream(torch.cuda.current_stream(gb.device))
-            state = [t.clone() for t in (gb.params, gb.adam_m, gb.adam_v, gb.adam_t, gb.flags)]
-            with torch.cuda.stream(st):
+            with _optimiser_state_kept([gb], gb.device, warm_stream=st), torch.cuda.stream(st):
                 self.enqueue(cfg)           # warm-up outside the capture (module load); its optimiser update is undone
-            torch.cuda.current_stream(gb.device).wait_stream(st)
-            torch.cuda.synchronize(gb.device)
-            for t, saved in zip((gb.params, gb.adam_m, gb.adam_v, gb.adam_t, gb.flags), state):
-                t.copy_(saved)
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, stream=st):
                 self.enqueue(cfg)
@@ -1033,15 +1020,10 @@ class GuidanceGroup:
         self.graphs, self.joint, self.multi = [], None, []
         if joint and len(self.batches) > 1:
             main = torch.cuda.Stream(self.device)
-            saved = [[t.clone() for t in (gb.params, gb.adam_m, gb.adam_v, gb.adam_t, gb.flags)] for gb in self.batches]
-            for gb, st in zip(self.batches, self.streams):      # warm-up launches outside the capture (module load)
-                with torch.cuda.stream(st):
-                    gb.step(cfg)
-            torch.cuda.synchronize(self.device)
-            for gb, sv in zip(self.batches, saved):             # ... whose optimiser update is undone
-                for t, s0 in zip((gb.params, gb.adam_m, gb.adam_v, gb.adam_t, gb.flags), sv):
-                    t.copy_(s0)
-            torch.cuda.synchronize(self.device)
+            with _optimiser_state_kept(self.batches, self.device):      # warm-up launches outside the capture (module load)
+                for gb, st in zip(self.batches, self.streams):
+                    with torch.cuda.stream(st):
+                        gb.step(cfg)
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, stream=main):
                 for gb, st in zip(self.batches, self.streams):
@@ -1062,7 +1044,7 @@ class GuidanceGroup:
 
     def run(self, cfg, n):
         """n iterations of every batch: multi-iteration graphs while they fit, single-iteration replays for the rest."""
-        k = getattr(self, "steps_per_graph", 1)
+        k = self.steps_per_graph
         done = 0
         while k > 1 and self.multi and n - done >= k:
             for g, st in zip(self.multi, self.streams):
@@ -1074,7 +1056,7 @@ class GuidanceGroup:
 
     def step(self, cfg):
         """One iteration of every batch: graph replay when captured, eager launches otherwise."""
-        if getattr(self, "joint", None) is not None:
+        if self.joint is not None:
             with torch.cuda.stream(self.main):
                 self.joint.replay()
             return
@@ -1087,7 +1069,7 @@ class GuidanceGroup:
 
     def restart(self, params):
         """New denoising step: the given (16,) parameter vector for every image and a fresh optimiser (PL:1478)."""
-        joint = getattr(self, "joint", None) is not None
+        joint = self.joint is not None
         for gb, st in zip(self.batches, self.streams):
             with torch.cuda.stream(self.main if joint else st):   # the joint graph replays on the capture stream
                 gb.params.copy_(params.to(gb.params.device).expand_as(gb.params))
@@ -1118,6 +1100,15 @@ class GuidanceGroup:
                 gb.load_scenes(c)
 
 
+def _normal_rgb(hit, sd, col, sigma):
+    """The normal map of render_normal_and_disparity (PL:272-289) from per-pixel hit mask, signed edge distance and summed
+    vertex normals of the hit face: soft coverage, blend with a white background, min-max normalisation, black background."""
+    p = torch.sigmoid(-sd / sigma)
+    rgb = torch.where(hit[:, None], (p[:, None] * col + 1e-10) / (p[:, None] + 1e-10), torch.ones_like(col))
+    nn = (rgb - rgb.min()) / (rgb.max() - rgb.min() + 1e-6)
+    return torch.where(hit[:, None], nn, torch.zeros_like(nn))
+
+
 def normal_map(gb, face_set, r=0, b=0, sigma=1e-8):
     """(H, W, 3) normal map of render r of image b as render_normal_and_disparity returns it (PL:272-289), read back from
     the G-buffer the last step left (face ids, edge distances, vertex normals) -- debug dumps only."""
@@ -1130,11 +1121,8 @@ def normal_map(gb, face_set, r=0, b=0, sigma=1e-8):
     hit = p2f >= 0
     f0 = m["f_off"] + (m["Fh"] if face_set == L.FACES_OBJ else 0)
     f = gb.faces.long()[(p2f.clamp(min=0) + f0).clamp(max=gb.faces.shape[0] - 1)]
-    col = vn[f].sum(1)
-    p = torch.sigmoid(-torch.where(hit, sd, torch.zeros_like(sd)) / sigma)
-    rgb = torch.where(hit[:, None], (p[:, None] * col + 1e-10) / (p[:, None] + 1e-10), torch.ones_like(col))
-    nn = (rgb - rgb.min()) / (rgb.max() - rgb.min() + 1e-6)
-    return torch.where(hit[:, None], nn, torch.zeros_like(nn)).reshape(gb.H, gb.W, 3).cpu().numpy()
+    nn = _normal_rgb(hit, torch.where(hit, sd, torch.zeros_like(sd)), vn[f].sum(1), sigma)
+    return nn.reshape(gb.H, gb.W, 3).cpu().numpy()
 
 
 def save_grid(img1, img2, path):
@@ -1149,6 +1137,23 @@ def save_grid(img1, img2, path):
     Image.fromarray((out * 255.0 + 0.5).astype(np.uint8)).save(path)
 
 
+def _blank_scene(H, W, **overrides):
+    """A scene of nothing -- no hand, no object, blank maps -- for batches that only render a mesh given as the object."""
+    scene = dict(obj_verts=np.zeros((0, 3), np.float32), obj_faces=np.zeros((0, 3), np.int64), hand_verts=np.zeros((0, 3), np.float32),
+                 hand_faces=np.zeros((0, 3), np.int64), T_h2m=np.eye(4, dtype=np.float32),
+                 J_regressor=np.zeros((16, 1), np.float32), kps_2d=np.zeros((21, 2), np.float32),
+                 moge_normal=np.zeros((H, W, 3), np.float32), moge_disp=np.zeros((H, W), np.float32),
+                 hand_mask=np.zeros((H, W), bool), obj_mask=np.zeros((H, W), bool), fov=60.0, H=H, W=W)
+    scene.update(overrides)
+    return scene
+
+
+def _mesh_render_cfg():
+    cfg, _ = phase_cfg("B", do_update=False)
+    cfg.world_space_input = 1     # the reference renders the target mesh as it is (PL:1247-1256)
+    return cfg
+
+
 class TargetRenderer:
     """Target maps of an image on the DEVICE: the reference renders the MoGe image mesh once per image with
     render_normal_and_disparity (PL:272-289, called at PL:1247-1256 on the mesh as it is) and masks the two maps with the
@@ -1160,18 +1165,15 @@ class TargetRenderer:
 
     def __init__(self, H, W, vcap, fcap, device="cuda"):
         self.H, self.W, self.vcap, self.fcap = int(H), int(W), int(vcap), int(fcap)
-        dummy = dict(obj_verts=np.zeros((self.vcap, 3), np.float32), obj_faces=np.zeros((self.fcap, 3), np.int64),     # sizes only
-                     hand_verts=np.zeros((0, 3), np.float32),
-                     hand_faces=np.zeros((0, 3), np.int64), T_h2m=np.eye(4, dtype=np.float32),
-                     J_regressor=np.zeros((16, 1), np.float32), kps_2d=np.zeros((21, 2), np.float32),
-                     moge_normal=np.zeros((H, W, 3), np.float32), moge_disp=np.zeros((H, W), np.float32),
-                     hand_mask=np.zeros((H, W), bool), obj_mask=np.zeros((H, W), bool), fov=60.0, H=H, W=W)
+        dummy = _blank_scene(H, W, obj_verts=np.zeros((self.vcap, 3), np.float32), obj_faces=np.zeros((self.fcap, 3), np.int64))     # sizes only
         gb = self.gb = GuidanceBatch([dummy], device=device, n_renders=1, grid_res=2, topology="deferred")
         dev = gb.device
         self.topo_ws = torch.empty(gb.lib.foho_topology_workspace_bytes(self.vcap), dtype=torch.uint8, device=dev)
         self.flags = torch.zeros(2, dtype=torch.int32, device=dev)
-        self.cfg, _ = phase_cfg("B", do_update=False)
-        self.cfg.world_space_input = 1
+        self.cfg = _mesh_render_cfg()
+        # Not GuidanceBatch._upload's mirrors: those belong to ONE load at a time and wait for its event; several renders of
+        # this renderer are in flight at once, each staged in mirrors of its own (`key`) that its caller does not reuse before
+        # the image is done -- no event, no wait.
         self._mirrors = {}
 
     def fits(self, verts, faces, H, W):
@@ -1194,14 +1196,9 @@ class TargetRenderer:
         pv.numpy()[:v] = verts
         pf.numpy()[:f] = faces
         # this render's own sizes: the step takes every bound from dims / the image record, the buffers keep the capacity
-        m, im, d = gb.meta[0], gb._images_host[0], gb.dims
-        m.update(Vo=v, Fo=f)
-        im.Vo, im.Fo = v, f
-        im.k00, im.k11 = fov_focal(float(fov))
-        d.Vtot, d.Ftot, d.Vmax, d.Fmax, d.Vo_max, d.Fo_max = v, f, v, f, v, f
-        gb.Vtot, gb.Ftot = v, f
-        gb._desc = None
-        pim.numpy()[...] = np.frombuffer(bytes(im), np.uint8)
+        gb._set_object_sizes(v, f)
+        write_camera(gb._images_host[0], fov)
+        pim.numpy()[...] = _image_bytes(gb._images_host)
         gb.verts_in[:v].copy_(pv[:v], non_blocking=True)
         gb.faces[:f].copy_(pf[:f], non_blocking=True)
         gb.images.copy_(pim, non_blocking=True)
@@ -1225,12 +1222,7 @@ def _maps_from_gbuffer(gb, P):
     sd = gb.region("sdist", torch.float32, (P,))
     vn = gb.region("vn", torch.float32, (-1, 3))
     hit = p2f >= 0
-    f = gb.faces.long()[p2f.clamp(min=0)]
-    col = vn[f].sum(1)
-    p = torch.sigmoid(-sd / 1e-8)
-    rgb = torch.where(hit[:, None], (p[:, None] * col + 1e-10) / (p[:, None] + 1e-10), torch.ones_like(col))
-    nn = (rgb - rgb.min()) / (rgb.max() - rgb.min() + 1e-6)
-    nn = torch.where(hit[:, None], nn, torch.zeros_like(nn))
+    nn = _normal_rgb(hit, sd, vn[gb.faces.long()[p2f.clamp(min=0)]].sum(1), 1e-8)
     depth = torch.where(hit, z, torch.full_like(z, 10.0))
     disp = 1 / (depth + 1e-6)
     disp = (disp - disp.min()) / (disp.max() - disp.min() + 1e-6)
@@ -1243,17 +1235,9 @@ def hip_render_fn(device="cuda"):
     render_normal_and_disparity (PL:272-289)."""
 
     def render(verts, faces, H, W, fov):
-        verts = np.asarray(verts, np.float32)
-        faces = np.asarray(faces, np.int64)
-        dummy = dict(obj_verts=verts, obj_faces=faces, hand_verts=np.zeros((0, 3), np.float32),
-                     hand_faces=np.zeros((0, 3), np.int64), T_h2m=np.eye(4, dtype=np.float32),
-                     J_regressor=np.zeros((16, 1), np.float32), kps_2d=np.zeros((21, 2), np.float32),
-                     moge_normal=np.zeros((H, W, 3), np.float32), moge_disp=np.zeros((H, W), np.float32),
-                     hand_mask=np.zeros((H, W), bool), obj_mask=np.zeros((H, W), bool), fov=fov, H=H, W=W)
+        dummy = _blank_scene(H, W, obj_verts=verts, obj_faces=faces, fov=fov)
         gb = GuidanceBatch([dummy], device=device, n_renders=1, grid_res=2, topology="render")
-        cfg, _ = phase_cfg("B", do_update=False)
-        cfg.world_space_input = 1     # the reference renders the target mesh as it is (PL:1247-1256)
-        gb.step(cfg, stages=L.STAGE_VERTEX | L.STAGE_RASTER)
+        gb.step(_mesh_render_cfg(), stages=L.STAGE_VERTEX | L.STAGE_RASTER)
         torch.cuda.current_stream(gb.device).synchronize()     # this stream only: loader threads render next to a running job
         gb.raise_on_flags()
         nn, disp, p2f = _maps_from_gbuffer(gb, H * W)

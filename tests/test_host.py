@@ -1,4 +1,5 @@
 """Host-side logic on CPU: CSR builders, phase recipes, mesh IO, image sharding and the gloo metrics all-reduce."""
+import ctypes
 import os
 import socket
 import subprocess
@@ -82,6 +83,119 @@ def test_phase_recipes_match_the_reference_weights():
     assert c.eps == pytest.approx(1e-4) and c.blur_radius == pytest.approx(np.log(1 / 1e-4 - 1) * 1e-8, rel=1e-6)
     with pytest.raises(ValueError):
         E.phase_cfg("D")
+
+
+def _two_scenes(H=6, W=10):
+    """Two hand-made scenes (no renderer): different fov, hand poses, objects and masks; scene 0 brings its own camera, scene 1 relies on
+    the defaults; scene 1 comes in float64 / int32 / nested lists to exercise the conversions."""
+    rng = np.random.default_rng(5)
+    hv, hf = synthetic.hand_template()
+    jr = rng.random((16, len(hv))).astype(np.float32)
+    scenes = []
+    for k, (level, fov) in enumerate(((1, 35.0), (2, 60.0))):
+        ov, of = synthetic.icosphere(level, 0.04)
+        T = np.eye(4, dtype=np.float32)
+        T[:3, :4] = rng.normal(size=(3, 4))
+        Rm = synthetic.axis_angle_matrix([0.1 * k, -0.3, 0.2 + k])
+        sc = dict(hand_verts=(hv @ Rm.T.astype(np.float32) + np.float32(0.01 * k)).astype(np.float32), hand_faces=hf, obj_verts=ov + np.float32(0.02), obj_faces=of,
+                  T_h2m=T, J_regressor=jr.copy(), kps_2d=rng.random((21, 2)).astype(np.float32) * W, moge_normal=rng.random((H, W, 3)).astype(np.float32),
+                  moge_disp=rng.random((H, W)).astype(np.float32), hand_mask=rng.random((H, W)) < 0.4, obj_mask=rng.random((H, W)) < 0.4, fov=fov, H=H, W=W)
+        scenes.append(sc)
+    scenes[0].update(cam_R=synthetic.axis_angle_matrix([0.2, 0.1, -0.4]), cam_T=np.array([0.01, -0.02, 0.3]))
+    scenes[1].update(hand_verts=scenes[1]["hand_verts"].astype(np.float64), obj_faces=scenes[1]["obj_faces"].astype(np.int32),
+                     kps_2d=scenes[1]["kps_2d"].tolist(), T_h2m=scenes[1]["T_h2m"].astype(np.float64))
+    return scenes
+
+
+def _check_shared_fields(pk, scenes):
+    """Everything of a pack that does not depend on the object slots, against values computed here."""
+    H, W = scenes[0]["H"], scenes[0]["W"]
+    assert (pk.B, pk.H, pk.W) == (2, H, W)
+    for b, (s, im, m) in enumerate(zip(scenes, pk.images, pk.meta)):
+        assert (im.k00, im.k11) == E.fov_focal(s["fov"]) and m["fov"] == s["fov"]
+        assert im.k00 == pytest.approx(1.0 / np.tan(np.radians(s["fov"]) / 2), rel=1e-6)     # FoVPerspectiveCameras, aspect 1
+        assert (im.znear, im.zfar) == (np.float32(0.01), np.float32(100.0))
+        R = np.asarray(s["cam_R"], np.float32) if "cam_R" in s else np.diag([-1, 1, -1]).astype(np.float32)
+        T = np.asarray(s["cam_T"], np.float32) if "cam_T" in s else np.zeros(3, np.float32)
+        assert np.array_equal(np.array(im.cam_R, np.float32), R.reshape(-1)) and np.array_equal(np.array(im.cam_T, np.float32), T)
+        assert np.array_equal(np.array(im.T_h2m, np.float32).reshape(3, 4), np.asarray(s["T_h2m"], np.float32)[:3])       # rows 0-2, row-major
+        assert im.jcols == 778 and (im.Vh, im.Fh) == (778, 1552) == (m["Vh"], m["Fh"])
+        assert (im.v_off, im.f_off) == (m["v_off"], m["f_off"]) and im.n_edges == 0
+        hv = np.asarray(s["hand_verts"], np.float32)
+        assert np.array_equal(pk.verts[m["v_off"]:m["v_off"] + 778], hv)
+        assert np.array_equal(pk.hand_faces[b], np.asarray(s["hand_faces"]) + m["v_off"]) and pk.hand_faces[b].dtype == np.int32
+        assert np.array_equal(pk.hand_order[b], E.morton_order(hv) - np.arange(778))
+        hm, om = np.asarray(s["hand_mask"]), np.asarray(s["obj_mask"])
+        assert np.array_equal(pk.mask[b] & 1, hm) and np.array_equal(pk.mask[b] >> 1, om) and pk.mask.dtype == np.uint8
+        assert np.array_equal(pk.kps_2d[b], np.asarray(s["kps_2d"], np.float32))
+        assert np.array_equal(pk.tgt_normal[b], s["moge_normal"]) and np.array_equal(pk.tgt_disp[b], s["moge_disp"])
+    assert pk.hand_order.shape == (2, 778) and pk.hand_order.dtype == np.int32
+    assert sorted((pk.hand_order[0] + np.arange(778)).tolist()) == list(range(778))      # a permutation, stored as a delta on the lane
+    assert np.array_equal(pk.J, scenes[0]["J_regressor"]) and pk.J.dtype == np.float32
+    assert pk.params.shape == (2, 16) and pk.params.dtype == np.float32 and np.array_equal(pk.params[1], E.IDENTITY_PARAMS)
+    assert E.IDENTITY_PARAMS.tolist() == [1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0]      # PARAM_SLICES: scale, trans, unit quaternion; hand, object
+    assert pk.verts.dtype == np.float32 and ctypes.sizeof(pk.images[0]) == 144
+
+
+def test_scene_packer_exact_size_mode():
+    scenes = _two_scenes()
+    pk = E.pack_scenes(scenes)
+    _check_shared_fields(pk, scenes)
+    v_off = f_off = 0
+    for s, im, m in zip(scenes, pk.images, pk.meta):
+        Vo, Fo = len(s["obj_verts"]), len(s["obj_faces"])
+        assert (im.v_off, im.f_off, im.Vo, im.Fo) == (v_off, f_off, Vo, Fo) == (m["v_off"], m["f_off"], m["Vo"], m["Fo"])
+        assert m["n_edges"] == 0 and "Vcap" not in m                                     # the edge count is the topology tables'
+        assert np.array_equal(pk.verts[v_off + 778:v_off + 778 + Vo], s["obj_verts"])
+        assert np.array_equal(pk.faces[f_off:f_off + 1552], np.asarray(s["hand_faces"]) + v_off)
+        assert np.array_equal(pk.faces[f_off + 1552:f_off + 1552 + Fo], np.asarray(s["obj_faces"]) + v_off + 778)
+        v_off, f_off = v_off + 778 + Vo, f_off + 1552 + Fo
+    assert (pk.Vtot, pk.Ftot) == (v_off, f_off) == (len(pk.verts), len(pk.faces)) == (2 * 778 + 42 + 162, 2 * 1552 + 80 + 320)
+    assert pk.faces.dtype == np.int32
+    assert pk.obj_faces64 is None and pk.counts is None
+    blank = [{k: v for k, v in s.items() if not k.startswith("moge_")} for s in scenes]
+    assert E.pack_scenes(blank).tgt_normal is None and E.pack_scenes([scenes[0], blank[1]]).tgt_disp is None     # absent unless every image has them
+
+
+@pytest.mark.parametrize("install", [False, True])
+def test_scene_packer_capacity_mode(install):
+    """Capacity-sized slots; the constructor's mode (install=False) ignores the scenes' objects, load_scenes' mode installs them.  Both
+    agree with the exact-size mode on everything that does not depend on the object slots (_check_shared_fields, same expected values)."""
+    scenes = _two_scenes()
+    vcap, fcap = 170, 330
+    pk = E.pack_scenes(scenes, (vcap, fcap), install=install)
+    _check_shared_fields(pk, scenes)
+    assert (pk.Vtot, pk.Ftot) == (2 * (778 + vcap), 2 * (1552 + fcap)) and len(pk.verts) == pk.Vtot
+    assert pk.obj_faces64.shape == (2, fcap, 3) and pk.obj_faces64.dtype == np.int64 and pk.counts.shape == (2, 3) and pk.counts.dtype == np.int32
+    for b, (s, im, m) in enumerate(zip(scenes, pk.images, pk.meta)):
+        Vo, Fo = (len(s["obj_verts"]), len(s["obj_faces"])) if install else (0, 0)
+        assert (im.v_off, im.f_off) == (b * (778 + vcap), b * (1552 + fcap))
+        assert (im.Vo, im.Fo, im.n_edges) == (0, 0, 0)                                    # the device fills the record (foho_object_update)
+        assert (m["Vcap"], m["Fcap"], m["Vo"], m["Fo"], m["n_edges"]) == (vcap, fcap, Vo, Fo, 3 * Fo // 2)
+        assert pk.counts[b].tolist() == [Vo, Fo, 0]
+        lo = im.v_off + 778
+        assert np.array_equal(pk.verts[lo:lo + Vo], s["obj_verts"][:Vo]) and not pk.verts[lo + Vo:lo + vcap].any()
+        assert np.array_equal(pk.obj_faces64[b, :Fo], np.asarray(s["obj_faces"])[:Fo]) and not pk.obj_faces64[b, Fo:].any()
+        if not install:     # a new batch's `faces`: the hand's rows, then placeholder rows that name the slot's first vertex (in bounds)
+            assert pk.faces.dtype == np.int32 and len(pk.faces) == pk.Ftot and np.array_equal(pk.faces[im.f_off:im.f_off + 1552], pk.hand_faces[b])
+            assert (pk.faces[im.f_off + 1552:im.f_off + 1552 + fcap] == lo).all()
+    if install:
+        assert pk.faces is None                                                           # the object rows are foho_object_update's
+        with pytest.raises(E.L.FohoError):
+            E.pack_scenes(scenes, (161, fcap), install=True)                              # scene 1's object has 162 vertices
+        E.pack_scenes(scenes, (161, fcap))                                                # ... which the constructor's mode never looks at
+
+
+@pytest.mark.parametrize("mode", [dict(), dict(capacity=(200, 400)), dict(capacity=(200, 400), install=True)])
+def test_scene_packer_refuses_a_second_regressor(mode):
+    scenes = _two_scenes()
+    E.pack_scenes(scenes, **mode)
+    scenes[1]["J_regressor"][3, 10] += 0.25
+    with pytest.raises(E.L.FohoError, match="J_regressor"):
+        E.pack_scenes(scenes, **mode)
+    scenes[1]["J_regressor"] = scenes[0]["J_regressor"][:, :700]
+    with pytest.raises(E.L.FohoError, match="J_regressor"):
+        E.pack_scenes(scenes, **mode)
 
 
 def test_meshio_roundtrip(tmp_path):

@@ -528,3 +528,31 @@ def test_a_batch_refuses_images_with_different_joint_regressors():
     if gb.fits([a, b]):
         with pytest.raises(L.FohoError):
             gb.load_scenes([a, b])
+
+
+@gpu
+def test_both_entry_points_pack_a_scene_the_same_way():
+    """One scene through GuidanceBatch(...) at its exact size, and through load_scenes() into a capacity-mode batch that was built from
+    ANOTHER scene: what the two leave on the device is the same, byte for byte -- the image record (once foho_object_update has written
+    Vo, Fo and n_edges = 3 Fo / 2 into the capacity batch's; one image, so both start at vertex / face 0), mask, key points, regressor,
+    parameters, hand-order table, the vertices up to the object's last one and the hand's faces.  Nothing differs legitimately."""
+    from followmyhold_amd import engine as E
+    scene, other = (_np_scene(make_scene("ico2", 64, 64, seed=s)) for s in (0, 1))
+    Vh, Fh, Vo, Fo = (len(scene[k]) for k in ("hand_verts", "hand_faces", "obj_verts", "obj_faces"))
+    exact = E.GuidanceBatch([scene], grid_res=16)
+    cap = E.GuidanceBatch([other], grid_res=16, obj_capacity=(Vo + 38, Fo + 80))
+    cap.set_params(0, scale_hand=[1.5], rot_obj=[0.0, 1.0, 0.0, 0.0])            # load_scenes returns them to the identity
+    assert cap.fits([scene])
+    cap.load_scenes([scene])
+    cap.raise_on_flags()
+    assert int(cap.load_flags.cpu()[0]) == 0
+    rec = E.L.FohoImage.from_buffer_copy(bytes(exact.images.cpu().numpy()))
+    assert (rec.Vh, rec.Vo, rec.Fh, rec.Fo, rec.n_edges) == (Vh, Vo, Fh, Fo, 3 * Fo // 2) and exact.images.numel() == 144
+    for name in ("images", "mask", "kps_2d", "J", "params"):
+        a, b = getattr(exact, name).cpu().numpy(), getattr(cap, name).cpu().numpy()
+        assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes(), name
+    order = [gb.region("hand_order", torch.int32, (1, Vh)).cpu().numpy() for gb in (exact, cap)]
+    assert np.array_equal(order[0], order[1]) and np.array_equal(order[0][0], E.morton_order(scene["hand_verts"]) - np.arange(Vh))
+    assert exact.verts_in[:Vh + Vo].cpu().numpy().tobytes() == cap.verts_in[:Vh + Vo].cpu().numpy().tobytes()
+    assert exact.faces.dtype == cap.faces.dtype == torch.int32 and torch.equal(exact.faces[:Fh].cpu(), cap.faces[:Fh].cpu())
+    assert np.array_equal(exact.params.cpu().numpy()[0], E.IDENTITY_PARAMS)
