@@ -133,7 +133,7 @@ def _declare(L, path, signatures):
 
 
 # the side libraries: libfoho_<name>.so exports foho_<name>_* (C ABI csrc/foho_<name>.h) and is of version FOHO_<NAME>_VERSION
-SIDE_VERSIONS = {"vol": 100, "sflexi": 100, "rastk": 101, "wflexi": 100}      # rastk 101 = foho_rastk_blend_fwd / _bwd
+SIDE_VERSIONS = {"vol": 100, "sflexi": 100, "rastk": 101, "wflexi": 100, "mreg": 100}      # rastk 101 = foho_rastk_blend_fwd / _bwd
 _sides = {}
 
 

@@ -1,4 +1,4 @@
-// foho_side.h -- what the side libraries (libfoho_vol.so, libfoho_sflexi.so, libfoho_rastk.so, libfoho_wflexi.so) share.  Internal: everything is in an
+// foho_side.h -- what the side libraries (libfoho_vol.so, libfoho_sflexi.so, libfoho_rastk.so, libfoho_wflexi.so, libfoho_mreg.so) share.  Internal: everything is in an
 // anonymous namespace, so a library that includes it exports nothing new.
 //
 // Host: the error string behind foho_<name>_last_error, fail / launched, blocks_for, and FOHO_SIDE_ENTRY_POINTS for the version and

@@ -40,6 +40,7 @@ class Meshes:
         f = faces[0] if isinstance(faces, (list, tuple)) else (faces[0] if faces.dim() == 3 else faces)
         self._v, self._f, self.textures = v, f.to(torch.int64), textures
         self._edges = None
+        self._topology = None
 
     device = property(lambda self: self._v.device)
 
@@ -64,6 +65,7 @@ class Meshes:
     def update_padded(self, new_verts_padded):
         m = Meshes([new_verts_padded[0]], [self._f], self.textures)
         m._edges = self._edges
+        m._topology = self._topology
         return m
 
     def edges_packed(self):
@@ -73,6 +75,12 @@ class Meshes:
             e = torch.sort(e, dim=1)[0]
             self._edges = torch.unique(e, dim=0)
         return self._edges
+
+    def topology(self):
+        """The index tables of ops.mesh_regularizers (mesh_reg.MeshTopology), built once per connectivity."""
+        if self._topology is None:
+            self._topology = ops.MeshTopology(self._f, self._v.shape[0])
+        return self._topology
 
     def verts_normals_packed(self):
         """Area-weighted vertex normals, normalised with eps 1e-6 (pytorch3d Meshes._compute_vertex_normals)."""
@@ -399,6 +407,23 @@ def mesh_edge_loss(meshes: Meshes, target_length: float = 0.0):
     e, v = meshes.edges_packed(), meshes.verts_packed()
     d = v[e[:, 0]] - v[e[:, 1]]
     return ((d.norm(dim=1, p=2) - target_length) ** 2.0).sum() / e.shape[0]
+
+
+def mesh_regularizers(meshes: Meshes, w_lap=0.0, lap_method="uniform", w_nc=0.0, w_edge=0.0, target_length=0.0):
+    """The three regularisers in one operator (ops.mesh_regularizers, libfoho_mreg.so): (total, terms [lap, nc, edge]).  No float
+    atomics, bitwise repeatable; the tables are cached on the Meshes and follow update_padded."""
+    return ops.mesh_regularizers(meshes.verts_packed(), meshes.topology(), w_lap=w_lap, lap_method=lap_method, w_nc=w_nc, w_edge=w_edge,
+                                 target_length=target_length)
+
+
+def mesh_laplacian_smoothing(meshes: Meshes, method: str = "uniform"):
+    """pytorch3d.loss.mesh_laplacian_smoothing for one mesh (formulas restated in csrc/foho_mreg.h; parity with pytorch3d unpinned)."""
+    return mesh_regularizers(meshes, w_lap=1.0, lap_method=method)[0]
+
+
+def mesh_normal_consistency(meshes: Meshes):
+    """pytorch3d.loss.mesh_normal_consistency for one mesh (formulas restated in csrc/foho_mreg.h; parity with pytorch3d unpinned)."""
+    return mesh_regularizers(meshes, w_nc=1.0)[0]
 
 
 def load_ply(path):

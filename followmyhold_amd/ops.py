@@ -11,6 +11,7 @@ from . import _lib as L
 from ._lib import _p, _stream
 from .sparse_flexi import flexicubes_sparse, flexicubes_sparse_grad, grid_axes  # noqa: F401  (the extractors on axis tables: sparse_flexi.py)
 from .weighted_flexi import flexicubes_weighted  # noqa: F401  (alpha, beta, gamma, training mode, all gradients: weighted_flexi.py)
+from .mesh_reg import MeshTopology, mesh_regularizers  # noqa: F401  (Laplacian, normal consistency, edge length, fused, with gradient: mesh_reg.py)
 
 
 def _need_cuda(*ts):
